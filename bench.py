@@ -1,13 +1,17 @@
 """Headline benchmark: training rays/sec of the Mip-NeRF 360 hot path (BASELINE.json: 1024-ray batch,
 64 proposal + 128 fine samples, NerfMLP 8x1024 + PropMLP 4x256, Kubric base gin) on N MI355X.
 
-    python bench.py --gpus N --steps K --warmup W        (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]      (N>1: launched by torch.distributed.run)
 
 A step = forward + losses + backward + RCCL all-reduce + clip/Adam + weight re-cast on one batch of
 synthetic rays already resident in HBM (data: synthetic).  Weak scaling: 1024 rays per GPU.
-Prints ONE JSON line (rank 0) with `roofline` for the dominant kernel (bf16 NT GEMM of the NerfMLP trunk,
-timed live with HIP events around its launches INSIDE extra train steps, on the stream they run on) and `cpu_baseline`
-(the oracle = CPU restatement of the reference, timed on a bounded sample at N=1)."""
+A plain run sets up, runs W warm-up steps, times ONE window of exactly K steps and prints ONE JSON line (rank 0): `value` (rays/s)
+and `ms_per_step` of that window.  --dump-outputs DIR writes what the K-th timed step returned (dump_outputs below).
+--full adds everything else the benchmark measures, in the same line: the K-step window repeated for --min-time seconds (`value` =
+the median window), `cpu_baseline` (the oracle = CPU restatement of the reference, timed on a bounded sample at N=1), the eval
+PSNR against the oracle, the fixed-batch and other-target rates, the host enqueue time, the exposed all-reduce time (N>1) and
+`roofline` for the dominant kernel (bf16 NT GEMM of the NerfMLP trunk, timed live with HIP events around its launches INSIDE extra
+train steps, on the stream they run on)."""
 import argparse
 import json
 import math
@@ -54,6 +58,38 @@ def synth_batch(n_patch, P, seed, device):
                     static_mask=f(np.ones(shp + (1,))), near=f(np.full(shp + (1,), 0.1)), far=f(np.full(shp + (1,), 1.2)),
                     embed_idx=f(np.zeros(shp + (1,)), np.int32), cam_idx=f(np.zeros(shp + (1,)), np.int32))
   return utils.Batch(rays=rays, rgb=f(rng.uniform(size=shp + (3,))))
+
+
+DUMP_CAP = 3 << 20      # elements kept of one dumped array (12 MB as float32)
+DUMP_LIMIT = 64 << 20   # bytes of one dump in all
+
+
+def dump_outputs(path, arrays):
+  """--dump-outputs: `arrays` (name -> tensor / array / scalar, what the last timed step handed back) as path/<name>.npy, float32
+  (float64 for integer and double values, which float32 would round).  An array of more than DUMP_CAP elements is written as a
+  fixed sample of DUMP_CAP of them: the flat indices np.random.default_rng(0).integers(0, n, DUMP_CAP), sorted -- the same for two
+  builds that return the same shapes, so their files compare element for element."""
+  os.makedirs(path, exist_ok=True)
+  total = 0
+  for name, a in arrays.items():
+    a = torch.as_tensor(a).detach()
+    if a.numel() > DUMP_CAP:
+      idx = np.sort(np.random.default_rng(0).integers(0, a.numel(), DUMP_CAP))
+      a = a.reshape(-1)[torch.from_numpy(idx).to(a.device)]
+    a = a.to(torch.float32 if a.is_floating_point() and a.element_size() <= 4 else torch.float64).cpu().numpy()
+    total += a.nbytes
+    assert total <= DUMP_LIMIT, f'--dump-outputs: more than {DUMP_LIMIT} bytes'
+    np.save(os.path.join(path, name.replace('/', '.') + '.npy'), a)      # (stat names hold leaf paths: 'NerfMLP_0/Dense_0')
+
+
+def _flatten(prefix, v, out):
+  """nested dict of the step's stats -> {'stats.losses.data': value, ...}"""
+  if isinstance(v, dict):
+    for k in sorted(v):
+      _flatten(f'{prefix}.{k}', v[k], out)
+  else:
+    out[prefix] = v
+  return out
 
 
 def instep_roofline(train_step, state, next_batch, gen, thr, steps=5):
@@ -396,14 +432,19 @@ def bench_nerfacto(args, device, world, rank):
       w = float(tmax.item())
     return w
   wins = [window()]
-  for _ in range(int(min(max(1, math.ceil(args.min_time / wins[0])), args.max_windows)) - 1):
+  if args.dump_outputs and rank == 0:
+    # what the last step of that window returned: its stats, the final level's rendering, and the state it updated
+    fin = res['levels'][-1]
+    dump_outputs(args.dump_outputs, {'stats': res['stats'], 'rgb': fin['rgb_out'], 'weights': fin['weights'], 'params': model.flat,
+                                     'adam_m': model.m, 'adam_v': model.v})
+  for _ in range((int(min(max(1, math.ceil(args.min_time / wins[0])), args.max_windows)) if args.full else 1) - 1):
     wins.append(window())
   dt = float(np.median(wins))
-  kernels = nerfacto_roofline(model, step, N) if world == 1 else None
+  kernels = nerfacto_roofline(model, step, N) if args.full and world == 1 else None
   # the same step with the grid-input gradients stored in 16 bits (what rounds 3-4 timed: in the half mode scaled gradients below
   # 6e-8 flush to zero there and skip their table atomics) -- a second model, a quarter of the timed budget
   half_grad = None
-  if world == 1 and model.dt and model.grid_grad_f32:
+  if args.full and world == 1 and model.dt and model.grid_grad_f32:
     m_main = model
     model = NerfactoModel(NerfactoConfig(**CFG5), device=device, compute_dtype=args.dtype, seed=20200823, grid_grad_f32=False)
     for _ in range(args.warmup):
@@ -446,10 +487,22 @@ def main():
   ap.add_argument('--dtype', default=None, choices=['bf16', 'fp32', 'fp16'],
                   help="compute dtype; default bf16 (BASELINE config 2) and, for --config cfg5, fp16 (the reference's enable_amp: half operands,\n"
                        "half table copies, dynamic loss scaling)")
-  ap.add_argument('--no-cpu-baseline', action='store_true')
+  ap.add_argument('--full', action='store_true',
+                  help='beside the headline: repeated windows (--min-time), the CPU baseline, eval PSNR against the oracle, fixed-batch and\n'
+                       'other-target rates, host enqueue time, exposed all-reduce time (N>1), the in-step roofline.  Off: one window of\n'
+                       '--steps steps, and the line holds the headline figures only')
+  ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                  help='write what the last step of the (first) timed window returned as DIR/<name>.npy: the stats, the advanced rng key\n'
+                       'and the train state it updated (parameters and Adam moments; arrays above 3 Mi elements as a fixed seeded sample).\n'
+                       '--config cfg5 (whose step returns a dict): the packed stats, the final level\'s rgb and weights, parameters and\n'
+                       'Adam moments; its step counter and sample draws live in the model and a torch.Generator and are not arrays.\n'
+                       'The inputs are the same for the same arguments, so two builds compare file for file.  With --full the dump is\n'
+                       'still of the FIRST window (step W + K), while `loss_last` / `train_psnr_last` in the line are those of the last\n'
+                       'window run: they equal the dumped stats only in a plain run')
+  ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave the CPU baseline and the eval-PSNR leg out')
   ap.add_argument('--min-time', type=float, default=8.0,
-                  help='repeat the K-step timed window until this many seconds of timed steps have run; value = median window')
-  ap.add_argument('--max-windows', type=int, default=400)
+                  help='with --full: repeat the K-step timed window until this many seconds of timed steps have run; value = median window')
+  ap.add_argument('--max-windows', type=int, default=400, help='with --full: at most this many windows')
   ap.add_argument('--scaling', default='weak', choices=['weak', 'strong'],
                   help='weak: 1024 rays per GPU (the default the driver runs); strong: 1024 rays in total, split over the GPUs '
                        '(BASELINE.md promises both curves)')
@@ -499,9 +552,9 @@ def main():
     return bench_nerfacto(args, device, world, rank)
   from nerf_hugs_amd.internal import configs, train_utils
   configs.clear_config()
-  # the CPU baseline runs FIRST (it used to run last: the driver's 5-s SMI poll then saw 12 s of idle GPU next to 2 s of work)
+  # the CPU baseline runs FIRST (it used to run last: a utilisation poll then saw 12 s of idle GPU next to 2 s of work)
   cpu_base = None
-  if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 'cfg2' and args.rays_per_gpu is None:
+  if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 'cfg2' and args.rays_per_gpu is None:
     cpu_base = cpu_baseline(20200823)
   gin = {'cfg2': GIN, 'cfg3': GIN_CFG3, 'cfg4': GIN_CFG4, 'ref360': GIN_REF360}[args.config]
   configs.parse_config_files_and_bindings(None, gin)
@@ -525,7 +578,7 @@ def main():
     P = 8
   config = configs.make_config(batch_size=rays_per_gpu * world)
   model, state, _, train_step, _ = train_utils.setup_model(config, 20200823, compute_dtype=args.dtype, device=device)
-  theta_init = state.flat.clone()      # (for the eval-PSNR leg: the render of a network that has structure, see below)
+  theta_init = state.flat.clone() if args.full else None      # (for the eval-PSNR leg: the render of a network that has structure, see below)
   from nerf_hugs_amd.internal import synthetic
 
   def make_batch(i, targets=None):
@@ -585,11 +638,16 @@ def main():
       w = float(tmax.item())
     return w
 
-  # One K-step window is 0.2 s at the default K: too short for a 5-s SMI poll or a +-2 % box-to-box drift to average
-  # out.  The K-step window is repeated until --min-time seconds of timed steps have run (the count is fixed from the
-  # first window's max-over-ranks time, so every rank runs the same number); `value` is the MEDIAN window.
+  # A plain run times ONE window: exactly --steps steps; `value` and `ms_per_step` are that window's.
+  # --full repeats the K-step window until --min-time seconds of timed steps have run (0.2 s at the default K is too short for
+  # clock and scheduler drift to average out; the count is fixed from the first window's max-over-ranks time, so every rank
+  # runs the same number) and reports the MEDIAN window.
   wins = [window()]
-  nwin = int(min(max(1, math.ceil(args.min_time / wins[0])), args.max_windows))
+  if args.dump_outputs and rank == 0:
+    # what the last step of that window handed back: (state, stats, rng) -- before any further step updates the state in place
+    dump_outputs(args.dump_outputs, {'params': state.flat, 'adam_m': state.m, 'adam_v': state.v, 'step': state.step, 'rng': gen,
+                                     **_flatten('stats', dict(stats.items()), {})})
+  nwin = int(min(max(1, math.ceil(args.min_time / wins[0])), args.max_windows)) if args.full else 1
   for _ in range(nwin - 1):
     wins.append(window())
   dt = float(np.median(wins))
@@ -598,7 +656,7 @@ def main():
   # the trunk's post-relu active fraction at this point of training: popcount of the 1-bit relu masks the forward NT GEMMs wrote
   # (they are in HBM for the backward pass): the operand statistics the GEMM times below belong to
   active = None
-  if rank == 0 and args.dtype == 'bf16':
+  if args.full and rank == 0 and args.dtype == 'bf16':
     try:
       eng = model.engine(device)
       lut = torch.tensor([bin(i).count('1') for i in range(256)], dtype=torch.int64, device=device)
@@ -611,26 +669,30 @@ def main():
     except Exception as e:      # (a measurement beside the headline: never fails the bench)
       active = {"error": repr(e)}
   eval_psnr = eval_psnr_init = None
-  if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 'cfg2' and args.rays_per_gpu is None:
+  if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == 'cfg2' and args.rays_per_gpu is None:
     eval_psnr = eval_psnr_vs_oracle(model, state, batch, args.dtype)
     # the same comparison at the INITIAL weights (he_uniform trunk), kept from round 5 for continuity
     eval_psnr_init = eval_psnr_vs_oracle(model, state, batch, args.dtype, flat=theta_init)
   # the same windows on ONE fixed batch (what rounds 1-4 reported): a quarter of the timed budget
-  fwins = [window(batch) for _ in range(max(3, nwin // 4))] if len(pool) > 1 else list(wins)
-  dt_fixed = float(np.median(fwins))
+  fwins = None
+  if args.full:
+    fwins = [window(batch) for _ in range(max(3, nwin // 4))] if len(pool) > 1 else list(wins)
+    dt_fixed = float(np.median(fwins))
   # host side of a step: wall time of enqueueing 8 steps onto an idle GPU without waiting for them (the launch queue is
   # far deeper than 8 steps); host_enqueue_ms >= ms_per_step means the step is host-bound
-  torch.cuda.synchronize()
-  t0 = time.perf_counter()
-  for _ in range(8):
-    state, stats, gen = train_step(gen, state, next_batch(), 0.5, thr)
-  host_ms = (time.perf_counter() - t0) / 8 * 1e3
-  torch.cuda.synchronize()
+  host_ms = None
+  if args.full:
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(8):
+      state, stats, gen = train_step(gen, state, next_batch(), 0.5, thr)
+    host_ms = (time.perf_counter() - t0) / 8 * 1e3
+    torch.cuda.synchronize()
   # N > 1: the part of the gradient exchange the backward pass does not hide (events on the compute stream around the point
   # where the step waits for its all-reduces; train_utils.AR_PROFILE), over 10 extra untimed steps -- so that a SCALE run
   # explains itself: ms_per_step(N) - ms_per_step(1) should be about this number
   ar_exposed = None
-  if world > 1:
+  if args.full and world > 1:
     train_utils.AR_PROFILE = []
     for _ in range(10):
       state, stats, gen = train_step(gen, state, next_batch(), 0.5, thr)
@@ -641,14 +703,14 @@ def main():
       dist.all_reduce(t_, op=dist.ReduceOp.MAX)
       ar_exposed = round(float(t_.item()), 4)
   roof = None
-  if args.dtype == 'bf16' and args.config in ('cfg2', 'ref360'):
+  if args.full and args.dtype == 'bf16' and args.config in ('cfg2', 'ref360'):
     # after the timed region: a few more steps with the GEMM launches bracketed by HIP events (every rank runs them:
     # the steps contain the gradient all-reduce; rank 0 reports)
     roof, roof_others, roof_shapes, state, gen = instep_roofline(train_step, state, next_batch, gen, thr)
   # LAST (it un-trains the network): the same windows on the OTHER target kind -- random colours when the headline pool is the scene
   other = 'random' if args.targets == 'scene' else 'scene'
   other_line = None
-  if len(pool) > 1:
+  if args.full and len(pool) > 1:
     pool_main, pool = pool, [make_batch(i, other) for i in range(min(len(pool), 32))]
     for _ in range(args.warmup):
       state, stats, gen = train_step(gen, state, next_batch(), 0.5, thr)
@@ -665,7 +727,7 @@ def main():
         "metric": "train rays/sec (%d-ray batch per GPU, %s samples)" % (rays_per_gpu, "64+64+32" if args.config == 'ref360' else "64+128"), "value": round(rps, 1), "unit": "rays/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3),
         "windows": len(wins), "timed_s": round(float(np.sum(wins)), 3), "gpu_timed_s": round(float(np.sum(wins)), 3),
-        "host_enqueue_ms_per_step": round(host_ms, 3), "step_graph": bool(getattr(train_step, 'graph_active', lambda: False)()),
+        "host_enqueue_ms_per_step": None if host_ms is None else round(host_ms, 3), "step_graph": bool(getattr(train_step, 'graph_active', lambda: False)()),
         "value_min": round(rays_per_gpu * world * args.steps / max(wins), 1), "value_max": round(rays_per_gpu * world * args.steps / min(wins), 1),
         "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": args.dtype,
         "data": (f"synthetic: {len(pool)} distinct pre-generated batches resident in HBM, one per step (no batch twice inside a window); "
@@ -673,9 +735,10 @@ def main():
                     else "independent random rays and colours")),
         ("random_targets" if other == 'random' else "scene_targets"): other_line,
         "trunk_relu_active_fraction": active,
-        "fixed_batch": {"value": round(rays_per_gpu * world * args.steps / dt_fixed, 1), "ms_per_step": round(dt_fixed / args.steps * 1e3, 3),
-                        "windows": len(fwins), "fresh_over_fixed": round(dt_fixed / dt, 4),
-                        "note": "every step on pool[0] (the rounds 1-4 protocol), timed after the headline windows"},
+        "fixed_batch": None if fwins is None else {
+            "value": round(rays_per_gpu * world * args.steps / dt_fixed, 1), "ms_per_step": round(dt_fixed / args.steps * 1e3, 3),
+            "windows": len(fwins), "fresh_over_fixed": round(dt_fixed / dt, 4),
+            "note": "every step on pool[0] (the rounds 1-4 protocol), timed after the headline windows"},
         "config": {"workload": {"cfg2": "configs[1]: MipNeRF360 base (kubric_1024_base.gin nets), 1024 rays x (64 prop + 128 fine) per GPU, "
                                         "full train step",
                                 "cfg3": "configs[2] restatement: + HuGS static masks, GLO 48, charb, 4096 rays x (64+128), full train step",

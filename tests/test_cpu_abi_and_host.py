@@ -179,27 +179,44 @@ def test_checkpoint_roundtrip(tmp_path):
   configs.clear_config()
 
 
-def test_every_reference_gin_file_parses():
-  """All 19 gin files of the reference load through the gin-subset reader and build a Model (or raise the
-  documented NotImplementedError).  Runs only where the reference checkout
-  exists (build container); the GPU box has no /root/reference."""
-  import glob
+def test_project_gin_files_parse_and_build(tmp_path):
+  """The gin texts this project states itself (bench.py's four workloads, the train-step tests' small shape and its variant with
+  a 64-wide PropMLP and the colour branch on), each written out as a gin FILE -- with a header comment, blank lines, a trailing
+  comment and a scoped binding -- and read through load_config: every one builds a Model (none is refused with
+  NotImplementedError), the 64-wide PropMLP is zero-padded to a tile, and statements outside the subset raise."""
+  import bench
   from nerf_hugs_amd.internal import configs, models
-  files = sorted(glob.glob('/root/reference/MipNeRF360/configs/*.gin'))
-  if not files:
-    pytest.skip('reference checkout not present')
-  built, refused = 0, []
-  for f in files:
+  from tests.test_gpu_train_step import SMALL
+  narrow = [g for g in SMALL if 'net_' not in g and 'disable_rgb' not in g] + [
+      "PropMLP.net_depth = 2", "PropMLP.net_width = 64", "NerfMLP.net_depth = 4", "NerfMLP.net_width = 128"]
+  texts = {'cfg2': bench.GIN, 'cfg3': bench.GIN_CFG3, 'cfg4': bench.GIN_CFG4, 'ref360': bench.GIN_REF360, 'small': SMALL, 'narrow': narrow}
+  built, refused = {}, []
+  for name, lines in texts.items():
+    p = tmp_path / f'{name}.gin'
+    p.write_text(f'# {name}: written by the test\n\n' + '\n\n'.join(lines) + "   # the last of the list\ntrain/Config.max_steps = 1234\n")
     configs.clear_config()
-    cfg = configs.load_config([f], ["Config.checkpoint_dir = None"], save_config=False)
+    cfg = configs.load_config([str(p)], ["Config.checkpoint_dir = None"], save_config=False)
+    assert cfg.max_steps == 1234 and cfg.checkpoint_dir is None
     try:
-      m = models.Model(cfg)
-      assert m.layout.num_params() > 0
-      built += 1
+      built[name] = models.Model(cfg)
+      assert built[name].layout.num_params() > 0
     except NotImplementedError:
-      refused.append(os.path.basename(f))
+      refused.append(name)
   configs.clear_config()
-  assert built == len(files) and refused == [], refused      # (debug.gin's 64-wide PropMLP is zero-padded to a tile)
+  assert len(built) == len(texts) and refused == [], refused
+  assert built['cfg2'].nerf_spec.net_width == 1024 and built['cfg2'].num_levels == 2 and built['ref360'].num_levels == 3
+  assert built['cfg4'].raydist == 'reciprocal' and built['cfg4'].nerf_spec.warp_fn is not None and built['cfg4'].num_glo_features == 4
+  assert built['cfg3'].num_glo_features == 48 and built['cfg2'].nerf_spec.warp_fn is None
+  lf = built['narrow'].layout.by_path[('PropMLP_0', 'Dense_0', 'kernel')]      # a 64-wide trunk is stored zero-padded to a tile
+  assert lf['shape'][1] == 64 and lf['pshape'][1] == 128
+  # outside the subset: include statements, macros, references to functions the path does not build, fields Config does not have
+  for bad in ("include 'other.gin'", "NEAR = 0.1", "Config.near = %NEAR", "Model.raydist_fn = @jnp.cosh"):
+    with pytest.raises((ValueError, SyntaxError)):
+      configs.parse_binding(bad)
+  configs.parse_config_files_and_bindings(None, ["Config.no_such_field = 1"])
+  with pytest.raises(ValueError):
+    configs.make_config()
+  configs.clear_config()
 
 
 def test_ctypes_prototypes_match_the_header():
@@ -307,31 +324,51 @@ def test_stat_tail_slots_do_not_overlap_for_any_level_count():
     train_utils._tail_slots(8)
 
 
-def test_nerfacto_yml_configs():
-  """nerfacto/configs/*.yml -> NerfactoConfig: every shipped nerfacto yml parses (the NeRF-W ones raise the NameError the
-  reference's own model dies with), and the restated BASELINE config-5 dictionary equals the yml.  Needs the reference
-  checkout (build container only)."""
-  import glob
+def test_nerfacto_yml_files_written_from_the_restated_config(tmp_path):
+  """yml file -> NerfactoConfig (nerfacto/configs.py load_yml / yml_to_kwargs), on yml files the test writes itself from the
+  project's restated BASELINE config-5 dictionary, in the layout the loader reads: a `base:` section (the train-script keys, of
+  which the loader takes its _BASE_KEYS and ignores the rest) and a `model:` section.  The base file gives the dictionary back;
+  the transient variants parse (HA-NeRF with its embedding; NeRF-W raises the NameError the reference's own model dies with);
+  a foreign model_type and the tiny-cuda-nn MLPs are refused; scene contraction fixes the bound at 2."""
+  import copy
   import yaml
-  ref = '/root/reference/nerfacto/configs'
-  if not os.path.isdir(ref):
-    pytest.skip('reference checkout not present')
   from nerf_hugs_amd.nerfacto import configs as C
+  lst = lambda v: list(v) if isinstance(v, tuple) else v
+  doc0 = {'base': {'seed': 1, 'model_type': 'nerfacto', 'dataset_type': 'synthetic', 'batch_size': 16384,
+                   **{k: lst(C.PHOTOTOURISM_NERFACTO_BASE[k]) for k in C._BASE_KEYS}},
+          'model': {'enable_tcnn_mlp': False, 'use_transient_embedding': False,
+                    **{k: lst(copy.deepcopy(v)) for k, v in C.PHOTOTOURISM_NERFACTO_BASE.items() if k not in C._BASE_KEYS}}}
+
+  def write(name, **model):
+    doc = copy.deepcopy(doc0)
+    doc['base'].update(model.pop('base', {}))
+    doc['model'].update(model)
+    p = tmp_path / f'{name}.yml'
+    p.write_text(f'# {name}: written by the test\n' + yaml.safe_dump(doc, sort_keys=False))
+    return str(p)
+
   seen = 0
-  for p in sorted(glob.glob(os.path.join(ref, '*nerfacto*.yml'))):
-    if 'nerfw' in p:
-      with pytest.raises(NameError):
-        C.load_yml(p)
-      continue
-    c = C.load_yml(p)
+  for name, model in (('base', {}), ('withmask', dict(transient_type='withmask')), ('robustnerf', dict(transient_type='robustnerf')),
+                      ('hanerf', dict(transient_type='hanerf', use_transient_embedding=True)),
+                      ('softplus', dict(density_activation='softplus')), ('shared', dict(use_same_proposal_network=True, proposal_net_args_list=doc0['model']['proposal_net_args_list'][:1])),
+                      ('one_level', dict(num_proposal_iterations=1, num_proposal_samples_per_ray=[256],
+                                         proposal_net_args_list=doc0['model']['proposal_net_args_list'][:1]))):
+    c = C.load_yml(write(name, **model))
     seen += 1
     assert c.num_proposal_iterations == len(c.num_proposal_samples_per_ray)
-    if 'hanerf' in p:
+    if name == 'hanerf':
       assert c.transient_type == 'hanerf' and c.use_transient_embedding
-  assert seen >= 10
-  kw = C.yml_to_kwargs(yaml.safe_load(open(os.path.join(ref, 'phototourism_nerfacto_base.yml'))))
+  assert seen == 7
+  with pytest.raises(NameError):
+    C.load_yml(write('nerfw', transient_type='nerfw', use_transient_embedding=True))
+  kw = C.yml_to_kwargs(yaml.safe_load(open(write('again'))))
   kw.pop('use_transient_embedding')
   assert kw == C.PHOTOTOURISM_NERFACTO_BASE
+  with pytest.raises(ValueError):
+    C.load_yml(write('nerf', base=dict(model_type='nerf')))
+  with pytest.raises(NotImplementedError):
+    C.load_yml(write('tcnn', enable_tcnn_mlp=True))
+  assert C.load_yml(write('contract', base=dict(enable_scene_contraction=True, bound=5))).bound == 2.0
 
 
 def test_stop_level_grad_false_is_refused_at_construction():

@@ -120,3 +120,81 @@ def test_cfg3_static_masks_glo48_charb_4096_rays():
 def test_cfg4_robustnerf_contract_reciprocal_glo4_1024_rays():
   import bench
   _at_size(bench.GIN_CFG4 + ["Config.randomized = True"], 4, 16, (0.05, 0.3), 1e6, 0.3, 16)
+
+
+def test_bench_plain_run_one_window_and_reproducible_dump(tmp_path):
+  """A plain `bench.py --gpus 1 --steps K --warmup W` run: one JSON line, ONE window of exactly K steps (`ms_per_step` and `value`
+  are that window's), nothing of the --full legs in the line; --dump-outputs writes float32 / float64 .npy files of at most 64 MB
+  in all -- the (state, stats, rng) that step W + K handed back -- and a second run with the same arguments writes the same bits
+  (the inputs are seeded and the step is bit-reproducible: test_bf16_1024_rays_step_properties)."""
+  import json
+  import os
+  import subprocess
+  import sys
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  K, W = 3, 3          # (W = 3: two eager steps and the capture, so the timed steps are replays as in a real run)
+  outs = []
+  for tag in ('a', 'b'):
+    d = str(tmp_path / tag)
+    out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', str(K), '--warmup', str(W),
+                          '--batch-pool', '8', '--dump-outputs', d], capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+    assert len(lines) == 1, out.stdout[-2000:]
+    outs.append((json.loads(lines[0]), d))
+  line = outs[0][0]
+  for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+    assert k in line, k
+  assert line['steps'] == K and line['warmup'] == W and line['windows'] == 1 and line['unit'] == 'rays/s' and line['dtype'] == 'bf16'
+  assert line['higher_is_better'] is True and line['value_min'] == line['value_max'] == line['value']
+  assert abs(line['timed_s'] - K * line['ms_per_step'] * 1e-3) <= 1e-3            # the window IS the K steps (both rounded to 3 digits)
+  assert abs(line['value'] - 1024 / (line['ms_per_step'] * 1e-3)) < 2e-3 * line['value']
+  for k in ('roofline', 'instep_kernels', 'cpu_baseline'):
+    assert k not in line, k
+  for k in ('fixed_batch', 'random_targets', 'host_enqueue_ms_per_step', 'trunk_relu_active_fraction', 'eval_psnr_vs_cpu_fp32_db'):
+    assert line[k] is None, k
+  names = sorted(os.listdir(outs[0][1]))
+  assert names == sorted(os.listdir(outs[1][1]))
+  for n in ('params.npy', 'adam_m.npy', 'adam_v.npy', 'step.npy', 'rng.npy', 'stats.loss.npy', 'stats.psnr.npy', 'stats.mses.npy'):
+    assert n in names, n
+  total = 0
+  for n in names:
+    a, b = np.load(os.path.join(outs[0][1], n)), np.load(os.path.join(outs[1][1], n))
+    assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+    assert np.array_equal(a, b), f'{n}: two runs with the same arguments differ'
+    total += os.path.getsize(os.path.join(outs[0][1], n))
+  assert total <= 64 << 20
+  assert float(np.load(os.path.join(outs[0][1], 'step.npy'))) == K + W
+  assert float(np.load(os.path.join(outs[0][1], 'stats.loss.npy'))) == pytest.approx(line['loss_last'], abs=1e-6)
+  assert np.abs(np.load(os.path.join(outs[0][1], 'adam_v.npy'))).max() > 0      # the state the steps updated, not its initial zeros
+
+
+def test_bench_cfg5_plain_run_dump(tmp_path):
+  """`bench.py --config cfg5 --dump-outputs`: the nerfacto step's set (packed stats, the final level's rgb and weights, parameters
+  and Adam moments as seeded samples) is float32 / float64, finite and at most 64 MB in all, from ONE window of K steps.  (No
+  run-to-run equality here: the table gradients are float atomics, whose order is not fixed.)"""
+  import json
+  import os
+  import subprocess
+  import sys
+  import bench
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  d = str(tmp_path / 'cfg5')
+  out = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--config', 'cfg5', '--steps', '2', '--warmup', '2',
+                        '--dump-outputs', d], capture_output=True, text=True, timeout=300, cwd=root)
+  assert out.returncode == 0, out.stderr[-3000:]
+  lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+  assert len(lines) == 1, out.stdout[-2000:]
+  line = json.loads(lines[0])
+  assert line['steps'] == 2 and line['windows'] == 1 and line['dtype'] == 'fp16' and line['ms_per_step'] > 0
+  for k in ('roofline', 'instep_kernels', 'with_16bit_grid_input_gradient'):
+    assert k not in line, k
+  assert sorted(os.listdir(d)) == ['adam_m.npy', 'adam_v.npy', 'params.npy', 'rgb.npy', 'stats.npy', 'weights.npy']
+  arrs = {n[:-4]: np.load(os.path.join(d, n)) for n in os.listdir(d)}
+  for n, a in arrs.items():
+    assert a.dtype in (np.float32, np.float64) and np.isfinite(a).all(), n
+  assert sum(os.path.getsize(os.path.join(d, n)) for n in os.listdir(d)) <= 64 << 20
+  assert arrs['rgb'].shape == (16384, 3) and arrs['weights'].shape == (16384, 128) and arrs['stats'].shape == (16,)
+  assert arrs['params'].shape == arrs['adam_m'].shape == arrs['adam_v'].shape == (bench.DUMP_CAP,)
+  assert arrs['rgb'].min() >= -1e-3 and arrs['rgb'].max() <= 1 + 1e-3 and arrs['weights'].min() >= 0 and arrs['weights'].max() <= 1
+  assert float(arrs['stats'][1]) == pytest.approx(line['loss_rgb_last'], abs=1e-6) and np.abs(arrs['adam_v']).max() > 0

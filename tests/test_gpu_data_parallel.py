@@ -149,7 +149,7 @@ def test_bench_two_ranks_on_one_gpu_prints_the_contract_line(form):
   env = dict(os.environ, HUGS_FORCE_DEVICE='0', HUGS_DIST_BACKEND='gloo')
   out = subprocess.run([sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
                         '--master-port', str(port), os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '3',
-                        '--min-time', '0', '--batch-pool', '4', '--step-graph', '1' if form == 'captured' else '0'],
+                        '--full', '--min-time', '0', '--batch-pool', '4', '--step-graph', '1' if form == 'captured' else '0'],
                        capture_output=True, text=True, env=env, timeout=600, cwd=root)
   assert out.returncode == 0, out.stderr[-3000:]
   lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
