@@ -304,6 +304,15 @@ long long hugs_ssim_ws_bytes(int H, int W, int C);
 int hugs_ssim(int H, int W, int C, const float* a, const float* b, float max_val, float filter_sigma, float k1, float k2,
               float* ws, float* out, void* stream);
 int hugs_mse(long long n, const float* a, const float* b, float* ws, float* out, void* stream);
+/* MipNeRF360/internal/image.py:82-124 color_correct on the device, fp64: img, ref, out [npix, nc] doubles (1 <= nc <= 4),
+ * out = img warped per channel by a quadratic + linear + bias fit to ref on the pixels inside [eps, 1-eps], re-fitted
+ * num_iters times (num_iters 0: out = img).  The fit is solved through fp64-MFMA normal equations and a Jacobi
+ * pseudo-inverse (eigenvalues <= 1e-12 of the largest dropped: the minimum-norm solution).  out may not alias img.
+ * ws: hugs_color_correct_ws_bytes(npix, nc) bytes, 8-byte aligned.  Deterministic; no host synchronisation. */
+long long hugs_color_correct_ws_bytes(long long npix, int nc);
+/* MipNeRF360/internal/image.py:82-124 (see above); -2 for a null pointer, npix <= 0, nc outside 1..4, num_iters < 0 */
+int hugs_color_correct(long long npix, int nc, int num_iters, double eps, const double* img, const double* ref,
+                       double* out, void* ws, void* stream);
 
 /* ---- HA-NeRF branch.  models.py:651-674 ImplicitMask: X = [pos_enc(pix_coords,0,deg,identity) |
  * tra_vec | 0-pad] [N,kpad] in the compute dtype (tra_vec NULL = zero_tra); its Dense+relu layers run on

@@ -70,6 +70,8 @@ _PROTOS = {
     'hugs_prng_step_jitter': 'pipppps',
     'hugs_ssim': 'iiippffffpps',
     'hugs_mse': 'qpppps',
+    'hugs_color_correct_ws_bytes': 'qi',
+    'hugs_color_correct': 'qiiipppps',       # (the fourth argument is a C double: _F64 below)
     'hugs_mask_input_fwd': 'iiippiips',
     'hugs_mask_head_fwd': 'iiipippps',
     'hugs_mask_head_bwd': 'iiiipippppps',
@@ -114,6 +116,9 @@ _PROTOS = {
 }
 _CT = {'i': ctypes.c_int, 'f': ctypes.c_float, 'p': ctypes.c_void_p, 'q': ctypes.c_longlong,
        's': ctypes.c_void_p}
+# The fp64 entries: their tensor arguments are float64 (every other entry refuses those), and the listed argument positions are
+# C `double` scalars.  The signature strings above keep to the i/f/q/p alphabet the header check reads, where a double reads 'i'.
+_F64 = {'hugs_color_correct': (3,)}
 
 
 class HugsError(RuntimeError):
@@ -167,6 +172,12 @@ class _Lib:
       fn = getattr(self.cdll, name)
       fn.argtypes = [_CT[c] for c in sig]
       fn.restype = ctypes.c_int
+    for name, where in _F64.items():
+      at = list(getattr(self.cdll, name).argtypes)
+      for i in where:
+        at[i] = ctypes.c_double
+      getattr(self.cdll, name).argtypes = at
+    self.cdll.hugs_color_correct_ws_bytes.restype = ctypes.c_longlong
 
   def declare(self, name, sig):
     _PROTOS[name] = sig
@@ -182,8 +193,11 @@ class _Lib:
       raise TypeError(f'{name}: expected {len(sig) - 1} args (+stream), got {len(args)}')
     conv = []
     dev = -1
-    for a, c in zip(args, sig):
-      if c == 'p':
+    f64 = _F64.get(name)
+    for i, (a, c) in enumerate(zip(args, sig)):
+      if f64 is not None and i in f64:
+        conv.append(float(a))
+      elif c == 'p':
         if a is None:
           conv.append(None)
         elif isinstance(a, torch.Tensor):
@@ -191,8 +205,9 @@ class _Lib:
             raise HugsError(f'{name}: tensor argument is not on the GPU (no CPU fallback)')
           if not a.is_contiguous():
             raise HugsError(f'{name}: tensor argument must be contiguous')
-          if a.dtype == torch.float64:
-            raise HugsError(f'{name}: float64 tensor passed to a float32 / bf16 kernel')
+          if (a.dtype == torch.float64) != (f64 is not None):
+            raise HugsError(f'{name}: float64 tensor passed to a float32 / bf16 kernel' if f64 is None else
+                            f'{name}: {a.dtype} tensor passed to a float64 kernel')
           if dev < 0:
             dev = a.get_device()
           elif a.get_device() != dev:

@@ -5,7 +5,8 @@ it (PSNR / SSIM, raw and colour-corrected), and write the output set a HuGS expe
 which is what the repository-level `metrics.py` / `scripts/metrics_*.sh` then read.
 
 Not rebuilt: flag parsing, the poll-for-new-checkpoints loop, tensorboard summaries and the turbo-colormapped depth
-PNGs (matplotlib): control plane / visualisation, out of scope.  Rendering and metrics run on the GPU.
+PNGs (matplotlib): control plane / visualisation, out of scope.  Rendering, colour correction (float64, image.color_correct_device), the metric quantisation and
+the metrics run on the GPU; an image goes to the host only where a file is written.
 """
 import functools
 import os
@@ -44,13 +45,13 @@ def evaluate(config, dataset, render_eval_fn, state, step=None, out_dir=None, ve
       continue
     torch.cuda.synchronize()
     render_times.append(time.time() - t0)
-    gt_rgb = batch.rgb.detach().cpu().numpy().astype(np.float64)
-    rgb = rendering['rgb'].detach().cpu().numpy().astype(np.float64)
-    rgb_cc = image.color_correct(rgb, gt_rgb)
+    gt_rgb = batch.rgb.detach().to(device=harness.device, dtype=torch.float64)      # float64 like eval.py:121-123, on the device
+    rgb = rendering['rgb'].detach().to(device=harness.device, dtype=torch.float64)
+    rgb_cc = image.color_correct_device(rgb, gt_rgb)
     m_rgb, m_cc, m_gt = rgb, rgb_cc, gt_rgb
     if config.eval_quantize_metrics:     # ensures that the images written to disk reproduce the metrics
-      m_rgb = np.round(m_rgb * 255) / 255
-      m_cc = np.round(m_cc * 255) / 255
+      m_rgb = torch.round(m_rgb * 255) / 255         # (half to even, like np.round)
+      m_cc = torch.round(m_cc * 255) / 255
     if config.eval_crop_borders > 0:
       c = config.eval_crop_borders
       m_rgb, m_cc, m_gt = m_rgb[c:-c, c:-c], m_cc[c:-c, c:-c], m_gt[c:-c, c:-c]

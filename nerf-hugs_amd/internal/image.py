@@ -2,8 +2,8 @@
 
 `MetricHarness` (image.py:127-141) runs on the device: the squared error and dm_pix's SSIM are HIP kernels
 (csrc/hugs_image.hip).  sRGB transfer curves (:48-67) and `downsample` (:70-79) are elementwise tensor code;
-`color_correct` (:82-124) keeps the reference's float64 host least squares (`np.linalg.lstsq`, which the
-reference itself prefers over the accelerator for stability)."""
+`color_correct` (:82-124) is the reference's float64 host least squares (`np.linalg.lstsq`), kept as the yardstick;
+`color_correct_device` is the same fit on the device in float64 (csrc/hugs_colorcc.hip), which eval.py uses."""
 import math
 
 import numpy as np
@@ -80,6 +80,26 @@ def color_correct(img, ref, num_iters=5, eps=0.5 / 255):
       warp.append(w)
     x = np.clip(a @ np.stack(warp, -1), 0, 1)
   return x.reshape(img.shape)
+
+
+def color_correct_device(img, ref, num_iters=5, eps=0.5 / 255):
+  """`color_correct` (image.py:82-124) on the device: `img`, `ref` are CUDA tensors [..., nc] (float32 or float64, nc <= 4),
+  the result is a float64 CUDA tensor of the same shape.  The fit runs in float64 like the host form (eval.py:121-123
+  casts the images up), through fp64-MFMA normal equations and a Jacobi pseudo-inverse (csrc/hugs_colorcc.hip)."""
+  if not (torch.is_tensor(img) and img.is_cuda and torch.is_tensor(ref) and ref.is_cuda):
+    raise L.HugsError('image.color_correct_device: inputs must be on the GPU (no CPU fallback)')
+  if img.shape[-1] != ref.shape[-1]:
+    raise ValueError(f'img\'s {img.shape[-1]} and ref\'s {ref.shape[-1]} channels must match')
+  if img.shape != ref.shape:
+    raise ValueError(f'shape mismatch {tuple(img.shape)} vs {tuple(ref.shape)}')
+  nc = img.shape[-1]
+  x = img.detach().to(torch.float64).contiguous()
+  r = ref.detach().to(torch.float64).contiguous()
+  npix = x.numel() // max(nc, 1)
+  ws = torch.empty(max(L.call('hugs_color_correct_ws_bytes', npix, nc) // 8, 1), dtype=torch.float64, device=x.device)
+  out = torch.empty_like(x)
+  L.call('hugs_color_correct', npix, nc, num_iters, eps, x, r, out, ws)
+  return out
 
 
 def _dev_f32(x, device):
