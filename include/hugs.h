@@ -314,6 +314,21 @@ long long hugs_color_correct_ws_bytes(long long npix, int nc);
 int hugs_color_correct(long long npix, int nc, int num_iters, double eps, const double* img, const double* ref,
                        double* out, void* ws, void* stream);
 
+/* ---- LPIPS (AlexNet), the third eval column: metrics.py:30-34,61 and nerfacto/eval.py:58-60
+ * (LearnedPerceptualImagePatchSimilarity(normalize=True, net_type='alex')), fp32 throughout (fp32-MFMA implicit-GEMM convolutions).
+ * a, b: [H,W,3] fp32 images in [0,1].  packed: the repacked weights, per layer l = 0..4 W [krows_l][Cout_l], bias [Cout_l],
+ * lin [Cout_l] with Cout = 64,192,384,256,256; conv1 rows are [ky 11][kx 12 (the last zero)][c 3] = 396, the others
+ * [ky][kx][Cin] = 1600, 1728, 3456, 2304 (internal/image.py LpipsAlex packs them); packed_floats is its length, checked.
+ * out[0] = LPIPS, out[1..5] = the five layer means.  maps: NULL, or the five per-pixel distance maps back to back
+ * (h_l*w_l floats each: h_0 = (H-7)/4+1, h_1 = (h_0-3)/2+1, h_2..4 = (h_1-3)/2+1, likewise w).
+ * ws: hugs_lpips_alex_ws_bytes(H,W) bytes (0 for a refused size); packed and ws 16-byte aligned.  H, W >= 31 (-2 otherwise:
+ * below that the second max-pool has no output).  Deterministic (no atomics); no host synchronisation. */
+/* metrics.py:30-34,61, nerfacto/eval.py:58-60 */
+long long hugs_lpips_alex_ws_bytes(int H, int W);
+/* metrics.py:30-34,61, nerfacto/eval.py:58-60 */
+int hugs_lpips_alex(int H, int W, const float* a, const float* b, const float* packed, long long packed_floats, float* ws,
+                    float* out, float* maps, void* stream);
+
 /* ---- HA-NeRF branch.  models.py:651-674 ImplicitMask: X = [pos_enc(pix_coords,0,deg,identity) |
  * tra_vec | 0-pad] [N,kpad] in the compute dtype (tra_vec NULL = zero_tra); its Dense+relu layers run on
  * hugs_gemm_nt / hugs_gemm_tn; head mask = sigmoid(X w + b) and its backward (d_raw [Npad] with zero tail rows,

@@ -72,6 +72,8 @@ _PROTOS = {
     'hugs_mse': 'qpppps',
     'hugs_color_correct_ws_bytes': 'qi',
     'hugs_color_correct': 'qiiipppps',       # (the fourth argument is a C double: _F64 below)
+    'hugs_lpips_alex_ws_bytes': 'ii',
+    'hugs_lpips_alex': 'iipppqppps',
     'hugs_mask_input_fwd': 'iiippiips',
     'hugs_mask_head_fwd': 'iiipippps',
     'hugs_mask_head_bwd': 'iiiipippppps',
@@ -178,6 +180,7 @@ class _Lib:
         at[i] = ctypes.c_double
       getattr(self.cdll, name).argtypes = at
     self.cdll.hugs_color_correct_ws_bytes.restype = ctypes.c_longlong
+    self.cdll.hugs_lpips_alex_ws_bytes.restype = ctypes.c_longlong
 
   def declare(self, name, sig):
     _PROTOS[name] = sig

@@ -1,8 +1,8 @@
 """The per-checkpoint body of the reference's eval.py (MipNeRF360/eval.py:83-228): render every test image, score
-it (PSNR / SSIM, raw and colour-corrected), and write the output set a HuGS experiment directory holds --
+it (PSNR / SSIM, and LPIPS when `lpips` is given; raw and colour-corrected), and write the output set a HuGS experiment directory holds --
 `NNNN_color.png`, `NNNN_gt.png`, `NNNN_colorcc.png`, `NNNN_acc.tiff`, `NNNN_distance_{mean,median}.tiff`,
 `metric_<name>_<step>.txt`, `metric_cc_<name>_<step>.txt`, `metric_mean_<step>.txt`, `render_times_<step>.txt` --
-which is what the repository-level `metrics.py` / `scripts/metrics_*.sh` then read.
+which is what the repository-level `metrics.py` / `scripts/metrics_*.sh` then read (here: nerf_hugs_amd.metrics).
 
 Not rebuilt: flag parsing, the poll-for-new-checkpoints loop, tensorboard summaries and the turbo-colormapped depth
 PNGs (matplotlib): control plane / visualisation, out of scope.  Rendering, colour correction (float64, image.color_correct_device), the metric quantisation and
@@ -20,9 +20,10 @@ from .internal import models
 from .internal import utils
 
 
-def evaluate(config, dataset, render_eval_fn, state, step=None, out_dir=None, verbose=False):
+def evaluate(config, dataset, render_eval_fn, state, step=None, out_dir=None, verbose=False, lpips=None):
   """eval.py:83-228 for one checkpoint.  `render_eval_fn` and `state` come from train_utils.setup_model;
-  `dataset` is a test-split internal.datasets.Dataset.  Returns (metrics, metrics_cc, render_times)."""
+  `dataset` is a test-split internal.datasets.Dataset.  `lpips`: an image.LpipsAlex (built from the user's weight files) adds
+  the 'lpips' metric and its files.  Returns (metrics, metrics_cc, render_times)."""
   step = int(state.step) if step is None else int(step)
   if out_dir is None:
     out_dir = os.path.join(config.checkpoint_dir, 'test_preds')
@@ -30,7 +31,7 @@ def evaluate(config, dataset, render_eval_fn, state, step=None, out_dir=None, ve
   rank0 = (not torch.distributed.is_initialized()) or torch.distributed.get_rank() == 0
   if config.eval_save_output and rank0:
     os.makedirs(out_dir, exist_ok=True)
-  harness = image.MetricHarness(state.flat.device)
+  harness = image.MetricHarness(state.flat.device, lpips=lpips)
   num_eval = min(dataset.size, config.eval_dataset_limit)
   metrics, metrics_cc, render_times = [], [], []
   train_frac = float(np.clip(step / config.max_steps, 0, 1))

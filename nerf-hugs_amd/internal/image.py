@@ -3,7 +3,9 @@
 `MetricHarness` (image.py:127-141) runs on the device: the squared error and dm_pix's SSIM are HIP kernels
 (csrc/hugs_image.hip).  sRGB transfer curves (:48-67) and `downsample` (:70-79) are elementwise tensor code;
 `color_correct` (:82-124) is the reference's float64 host least squares (`np.linalg.lstsq`), kept as the yardstick;
-`color_correct_device` is the same fit on the device in float64 (csrc/hugs_colorcc.hip), which eval.py uses."""
+`color_correct_device` is the same fit on the device in float64 (csrc/hugs_colorcc.hip), which eval.py uses.
+`LpipsAlex` is the reference's third metric (metrics.py:30-34,61, nerfacto/eval.py:58-60: LPIPS on AlexNet features) in fp32 on
+the device (csrc/hugs_lpips.hip), from weight files the user already has."""
 import math
 
 import numpy as np
@@ -133,12 +135,81 @@ def ssim(a, b, max_val=1.0, filter_sigma=1.5, k1=0.01, k2=0.03):
   return out[0]
 
 
-class MetricHarness:
-  """A helper class for evaluating several error metrics (image.py:127-141)."""
+# AlexNet `features` as torchvision defines it: (Cin, Cout, kernel), and where the weights sit in the two state dicts
+_ALEX = ((3, 64, 11), (64, 192, 5), (192, 384, 3), (384, 256, 3), (256, 256, 3))
+_ALEX_KEYS = tuple((f'features.{i}.weight', f'features.{i}.bias') for i in (0, 3, 6, 8, 10))      # torchvision alexnet
+_LIN_KEYS = tuple(f'lin{i}.model.1.weight' for i in range(5))                                      # the lpips package's alex.pth
 
-  def __init__(self, device='cuda'):
+
+class LpipsAlex:
+  """LPIPS with AlexNet features, `LearnedPerceptualImagePatchSimilarity(normalize=True, net_type='alex')` of the
+  reference (metrics.py:30-34,61, nerfacto/eval.py:58-60), as fp32 HIP kernels.  `conv_weights` / `conv_biases` /
+  `lin_weights` are five tensors each, in torch's [Cout, Cin, kh, kw] / [Cout] / [C] (or [1, C, 1, 1]) shapes; they are
+  repacked once into the [kh*kw*Cin][Cout] order the kernels read."""
+
+  def __init__(self, conv_weights, conv_biases, lin_weights, device='cuda'):
     self.device = torch.device(device)
+    if not (len(conv_weights) == len(conv_biases) == len(lin_weights) == 5):
+      raise ValueError('LpipsAlex takes five conv weights, five biases and five lin vectors')
+    parts = []
+    for (cin, cout, k), w, b, lin in zip(_ALEX, conv_weights, conv_biases, lin_weights):
+      w, b, lin = (torch.as_tensor(t).detach().to('cpu', torch.float32) for t in (w, b, lin))
+      if tuple(w.shape) != (cout, cin, k, k) or b.numel() != cout or lin.numel() != cout:
+        raise ValueError(f'LpipsAlex: expected a [{cout}, {cin}, {k}, {k}] conv with {cout} biases and lin weights, got '
+                         f'{tuple(w.shape)}, {tuple(b.shape)}, {tuple(lin.shape)}')
+      w = w.permute(2, 3, 1, 0)                                    # [kh, kw, Cin, Cout]
+      if cin == 3:
+        w = torch.cat([w, torch.zeros(k, 1, cin, cout)], 1)        # conv1: a twelfth, zero tap per kernel row
+      parts += [w.reshape(-1), b.reshape(-1), lin.reshape(-1)]
+    self.packed = torch.cat(parts).contiguous().to(self.device)
+
+  @classmethod
+  def from_files(cls, alexnet_path, lin_path, device='cuda'):
+    """`alexnet_path`: torchvision's AlexNet state dict; `lin_path`: the lpips package's alex.pth.  Local files only."""
+    alex = torch.load(alexnet_path, map_location='cpu', weights_only=True)
+    lin = torch.load(lin_path, map_location='cpu', weights_only=True)
+    for name, sd, keys in (('alexnet', alex, [k for p in _ALEX_KEYS for k in p]), ('lin', lin, list(_LIN_KEYS))):
+      missing = [k for k in keys if k not in sd]
+      if missing:
+        raise ValueError(f'LpipsAlex.from_files: {name} state dict lacks {missing}; keys found: {sorted(sd)}')
+    return cls([alex[w] for w, _ in _ALEX_KEYS], [alex[b] for _, b in _ALEX_KEYS], [lin[k] for k in _LIN_KEYS], device)
+
+  def __call__(self, a, b, return_layers=False):
+    """[H, W, 3] device tensors in [0, 1] -> LPIPS as a 0-d device tensor; with `return_layers` also the five layer means
+    (a [5] tensor) and the five per-pixel distance maps."""
+    if not (torch.is_tensor(a) and a.is_cuda and torch.is_tensor(b) and b.is_cuda):
+      raise L.HugsError('image.LpipsAlex: inputs must be on the GPU (no CPU fallback)')
+    if a.shape != b.shape or a.dim() != 3 or a.shape[-1] != 3:
+      raise ValueError(f'LpipsAlex takes two [H, W, 3] images, got {tuple(a.shape)} and {tuple(b.shape)}')
+    h, w, _ = a.shape
+    a, b = a.detach().to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous()
+    nbytes = L.call('hugs_lpips_alex_ws_bytes', h, w)
+    ws = torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=a.device)
+    out = torch.empty(6, dtype=torch.float32, device=a.device)
+    sizes, hh, ww = [], (h - 7) // 4 + 1, (w - 7) // 4 + 1
+    for i in range(5):
+      if i in (1, 2):
+        hh, ww = (hh - 3) // 2 + 1, (ww - 3) // 2 + 1
+      sizes.append((hh, ww))
+    maps = None
+    if return_layers and nbytes > 0:        # (a refused size: the call below raises before it touches anything)
+      maps = torch.empty(sum(y * x for y, x in sizes), dtype=torch.float32, device=a.device)
+    L.call('hugs_lpips_alex', h, w, a, b, self.packed, self.packed.numel(), ws, out, maps)
+    if not return_layers:
+      return out[0]
+    return out[0], out[1:], [m.reshape(s) for m, s in zip(maps.split([y * x for y, x in sizes]), sizes)]
+
+
+class MetricHarness:
+  """A helper class for evaluating several error metrics (image.py:127-141); with an `LpipsAlex` also 'lpips'."""
+
+  def __init__(self, device='cuda', lpips=None):
+    self.device = torch.device(device)
+    self.lpips = lpips
 
   def __call__(self, rgb_pred, rgb_gt, name_fn=lambda s: s):
     a, b = _dev_f32(rgb_pred, self.device), _dev_f32(rgb_gt, self.device)
-    return {name_fn('psnr'): float(mse_to_psnr(mse(a, b))), name_fn('ssim'): float(ssim(a, b))}
+    out = {name_fn('psnr'): float(mse_to_psnr(mse(a, b))), name_fn('ssim'): float(ssim(a, b))}
+    if self.lpips is not None:
+      out[name_fn('lpips')] = float(self.lpips(a, b))
+    return out
