@@ -515,6 +515,42 @@ int hugs_nf_adam_amp(long long n, float* theta, const float* grad, float* m, flo
                      const float* state, const float* bc, void* stream);
 int hugs_amp_update(float* state, float* counts, unsigned group_mask, float growth, float backoff, float interval, void* stream);
 
+/* HuGS static masks (HuGS/generate_static_mask.py after SAM; csrc/hugs_staticmask.hip).  Images are H x W with 3 <= H, W and
+ * H * W <= 2^24 (else -2); masks are [H,W] fp32 0/1 planes, read as value >= 0.5.  No entry synchronises with the host.
+ * hugs_sm_ws_bytes: workspace of hugs_sm_residual (what 0), hugs_sm_sfm_add for n masks (what 1), and the table of
+ *   hugs_sm_label_hist for n = S segments (what 2); -2 for a refused image size.
+ * hugs_sm_residual: generate_static_mask.py:269-275.  residual = mean_c |pred - gt|; thr[0] = its mean (fp64 sum in a fixed order,
+ *   rounded to fp32), thr[1] = torch.quantile(residual, q) (exact order statistics by radix select, fp32 lerp); mask_base =
+ *   residual <= thr[0]; mask_upper = mask_base | residual <= thr[1].
+ * hugs_sm_sfm_add: :344-374 for one batch of point-prompted SAM logits [N,H,W] and predicted IoUs [N].  keep[n] = (iou[n] >
+ *   iou_thresh, skipped when <= 0) & (stability >= stab_thresh, skipped when <= 0), stability = #(logit > mask_thr + stab_off) /
+ *   #(logit > mask_thr - stab_off) as int32 counts and a correctly rounded fp32 quotient (segment_anything's
+ *   calculate_stability_score); count[H,W] (int32, caller-held, zeroed by the caller before the first batch) += sum over kept n of
+ *   (logit > mask_thr).
+ * hugs_sm_label: :239-259 after the painting loop.  seg[H,W] int32 holds 0..S-1 or a negative value where no segment covers the
+ *   pixel; labels = seg where covered, else S + (smallest linear pixel index of the pixel's connected component of uncovered
+ *   pixels under the neighbourhood {up, down, left, right, up-left, down-right}) -- the partition the reference's loop builds.
+ * hugs_sm_label_hist + hugs_sm_select_erode: :128-145 intersect_masks for fine masks that partition the image, then :400-407
+ *   cv2.erode.  tab = [area | inter], 2 x (S + H*W) int32 indexed by label: area[l] = #(labels == l), inter[l] = #(labels == l &
+ *   coarse).  out = erode_k(selected[labels]) with selected[l] = (inter[l] * den >= num * area[l]) -- the rational form of
+ *   inter / area >= num / den; 1/2 is the reference's 0.5 -- and a k x k rectangle that nothing outside the image erodes (k = 1:
+ *   the intersect_masks result itself).
+ * hugs_sm_box: :110-125 fill_gap, :386-397 the combine + smooth step, a plain erode.  Source src 0: the mask a; 1: the int32 count
+ *   map a >= 1 (:377); 2: (a | b) & c of three masks (:386), also written to `combined` when not NULL.  pad 0 zeros (conv2d
+ *   'same'), 1 reflect (F.pad), 2 ones.  rule 0: out = m | (2 * box_k count >= k * k), the integer form of (box_k(m) + m) >= 0.5;
+ *   rule 1: out = (box_k count == k * k), erosion.  k odd, 1..15. */
+long long hugs_sm_ws_bytes(int what, int H, int W, int n);
+int hugs_sm_residual(int H, int W, const float* pred, const float* gt, float q, float* residual, float* mask_base,
+                     float* mask_upper, float* thr, void* ws, void* stream);
+int hugs_sm_sfm_add(int N, int H, int W, const float* logits, const float* iou, float iou_thresh, float mask_thr, float stab_off,
+                    float stab_thresh, int* count, int* keep, void* ws, void* stream);
+int hugs_sm_label(int H, int W, int S, const int* seg, int* labels, void* stream);
+int hugs_sm_label_hist(int H, int W, int S, const int* labels, const float* coarse, int* tab, void* stream);
+int hugs_sm_select_erode(int H, int W, const int* labels, const int* tab, int ntab, int num, int den, int k, float* out,
+                         void* stream);
+int hugs_sm_box(int H, int W, int src, const void* a, const float* b, const float* c, int k, int pad, int rule, float* combined,
+                float* out, void* stream);
+
 /* test/bench forms of hugs_gemm_nt / hugs_gemm_tn with an explicit kernel selection (a call argument: no process
  * state): tile_mode 0 = the default choice (what the plain entry points use), 1 = force the 128x128-tile kernels,
  * 3 = the 256x128 NT kernel where a 256x256 one would be chosen, 5 = 256x256 without the persistent form */

@@ -74,6 +74,13 @@ _PROTOS = {
     'hugs_color_correct': 'qiiipppps',       # (the fourth argument is a C double: _F64 below)
     'hugs_lpips_alex_ws_bytes': 'ii',
     'hugs_lpips_alex': 'iipppqppps',
+    'hugs_sm_ws_bytes': 'iiii',
+    'hugs_sm_residual': 'iippfppppps',
+    'hugs_sm_sfm_add': 'iiippffffppps',
+    'hugs_sm_label': 'iiipps',
+    'hugs_sm_label_hist': 'iiippps',
+    'hugs_sm_select_erode': 'iippiiiips',
+    'hugs_sm_box': 'iiipppiiipps',
     'hugs_mask_input_fwd': 'iiippiips',
     'hugs_mask_head_fwd': 'iiipippps',
     'hugs_mask_head_bwd': 'iiiipippppps',
@@ -181,6 +188,7 @@ class _Lib:
       getattr(self.cdll, name).argtypes = at
     self.cdll.hugs_color_correct_ws_bytes.restype = ctypes.c_longlong
     self.cdll.hugs_lpips_alex_ws_bytes.restype = ctypes.c_longlong
+    self.cdll.hugs_sm_ws_bytes.restype = ctypes.c_longlong
 
   def declare(self, name, sig):
     _PROTOS[name] = sig
