@@ -551,6 +551,27 @@ int hugs_sm_select_erode(int H, int W, const int* labels, const int* tab, int nt
 int hugs_sm_box(int H, int W, int src, const void* a, const float* b, const float* c, int k, int pad, int rule, float* combined,
                 float* out, void* stream);
 
+/* hugs_sm_sfm_add_lowres: :344-374 straight from the mask decoder's output.  lowres [N,3,256,256] logits and iou [N,3]; per prompt
+ *   the first highest-IoU mask (use_highest != 0, torch.argmax) or all three in order; the logit of an output pixel is SAM's
+ *   postprocess_masks (bilinear 256 -> 1024, crop to h_in x w_in, bilinear to H x W, align_corners = False) evaluated on the fly,
+ *   then the rules of the full-resolution entry above.  keep has N (use_highest) or 3 N entries; ws holds 12 N int32. */
+int hugs_sm_sfm_add_lowres(int N, int H, int W, int h_in, int w_in, const float* lowres, const float* iou, float iou_thresh,
+                           float mask_thr, float stab_off, float stab_thresh, int use_highest, int* count, int* keep, void* ws,
+                           void* stream);
+
+/* SAM's point prompt encoder + mask decoder (csrc/hugs_samdecode.hip), fp32: the predict_torch of generate_static_mask.py:346-351
+ * with multimask output, without the upsampling.  packed: the weights as nerf_hugs_amd.hugs.SamPointDecoder packs them (every
+ * matrix [in][out]; the length is checked).  hugs_sam_ws_bytes: N = 0: the per-image state; N >= 1: the workspace of a
+ * prediction of N prompts of P points (prompts run in chunks of 8, so it does not grow past that); -2 unless 1 <= P <= 10.
+ * hugs_sam_set_image: embedding [256,64,64] -> state (image tokens, dense positional encoding, and everything of the
+ * transformer that depends on the image alone).  hugs_sam_predict: coords [N,P,2] xy in model-input pixels, labels [N,P]
+ * int32 (1 foreground, 0 background) -> lowres [N,3,256,256], iou4 [N,4] (all four heads; multimask output is columns 1..3).
+ * ln_eps: the eps of the transformer's LayerNorms.  All pointers 16-byte aligned.  Deterministic; no host synchronisation. */
+long long hugs_sam_ws_bytes(int N, int P);
+int hugs_sam_set_image(const float* packed, long long packed_floats, const float* embedding, float* state, void* stream);
+int hugs_sam_predict(int N, int P, const float* coords, const int* labels, const float* packed, long long packed_floats, float ln_eps,
+                     const float* state, float* ws, float* lowres, float* iou4, void* stream);
+
 /* test/bench forms of hugs_gemm_nt / hugs_gemm_tn with an explicit kernel selection (a call argument: no process
  * state): tile_mode 0 = the default choice (what the plain entry points use), 1 = force the 128x128-tile kernels,
  * 3 = the 256x128 NT kernel where a 256x256 one would be chosen, 5 = 256x256 without the persistent form */

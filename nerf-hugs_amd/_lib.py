@@ -77,6 +77,10 @@ _PROTOS = {
     'hugs_sm_ws_bytes': 'iiii',
     'hugs_sm_residual': 'iippfppppps',
     'hugs_sm_sfm_add': 'iiippffffppps',
+    'hugs_sm_sfm_add_lowres': 'iiiiippffffippps',
+    'hugs_sam_ws_bytes': 'ii',
+    'hugs_sam_set_image': 'pqpps',
+    'hugs_sam_predict': 'iipppqfpppps',
     'hugs_sm_label': 'iiipps',
     'hugs_sm_label_hist': 'iiippps',
     'hugs_sm_select_erode': 'iippiiiips',
@@ -189,6 +193,7 @@ class _Lib:
     self.cdll.hugs_color_correct_ws_bytes.restype = ctypes.c_longlong
     self.cdll.hugs_lpips_alex_ws_bytes.restype = ctypes.c_longlong
     self.cdll.hugs_sm_ws_bytes.restype = ctypes.c_longlong
+    self.cdll.hugs_sam_ws_bytes.restype = ctypes.c_longlong
 
   def declare(self, name, sig):
     _PROTOS[name] = sig

@@ -251,6 +251,100 @@ __global__ void __launch_bounds__(SM_T) k_sfm_accum(int npix, int nchunk, int N,
     if (p + j < npix && a[j]) count[p + j] += a[j];
 }
 
+// ---------------------------------------------------------------- 2b. SfM masks from the decoder's 256 x 256 logits
+// SAM's postprocess_masks (bilinear 256 -> 1024, crop [:h_in, :w_in], bilinear -> H x W; align_corners = False) evaluated per
+// output pixel: each axis composes to two crop-grid taps of two low-res taps each.  The full-resolution logit is never stored:
+// k_lr_count recomputes it for the stability counts, k_lr_accum for the kept masks -- by the same function, so both passes see
+// the same bits.
+constexpr int LR = 256, LR_UP = 1024;
+struct LrAxis { int i[4]; float w[4]; };     // crop tap a = 0, 1: low-res taps i[2a], i[2a+1] with lambda w[2a+1]; w[0]: the crop taps' lambda
+
+// torch's area_pixel_compute_source_index + the index / lambda of upsample_bilinear2d, fp32
+__device__ __forceinline__ void lr_tap(int dst, float scale, int in, int& i0, int& i1, float& lam) {
+  const float s = fmaxf(((float)dst + 0.5f) * scale - 0.5f, 0.f);
+  i0 = min((int)s, in - 1);
+  i1 = i0 + (i0 < in - 1 ? 1 : 0);
+  lam = fminf(fmaxf(s - (float)i0, 0.f), 1.f);
+}
+
+__device__ __forceinline__ LrAxis lr_axis(int dst, float scale, int in) {
+  LrAxis a;
+  int c0, c1;
+  lr_tap(dst, scale, in, c0, c1, a.w[0]);
+  lr_tap(c0, (float)LR / (float)LR_UP, LR, a.i[0], a.i[1], a.w[1]);
+  lr_tap(c1, (float)LR / (float)LR_UP, LR, a.i[2], a.i[3], a.w[3]);
+  a.w[2] = 0.f;
+  return a;
+}
+
+__device__ __forceinline__ float lr_bilerp(float p00, float p01, float p10, float p11, float ly, float lx) {
+  return (1.f - ly) * ((1.f - lx) * p00 + lx * p01) + ly * ((1.f - lx) * p10 + lx * p11);
+}
+
+__device__ __forceinline__ float lr_logit(const float* __restrict__ L, const LrAxis& y, const LrAxis& x) {
+  float mid[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const float* r0 = L + y.i[2 * a] * LR;
+      const float* r1 = L + y.i[2 * a + 1] * LR;
+      mid[a][b] = lr_bilerp(r0[x.i[2 * b]], r0[x.i[2 * b + 1]], r1[x.i[2 * b]], r1[x.i[2 * b + 1]], y.w[2 * a + 1], x.w[2 * b + 1]);
+    }
+  return lr_bilerp(mid[0][0], mid[0][1], mid[1][0], mid[1][1], y.w[0], x.w[0]);
+}
+
+// mask j of the batch: the prompt's first highest-IoU mask (torch.argmax), or all 3 N in order; clears the counters
+__global__ void __launch_bounds__(SM_T) k_lr_select(int M, int highest, const float* __restrict__ iou, int* __restrict__ sel,
+                                                    float* __restrict__ iou_sel, int* __restrict__ cnt) {
+  const int j = blockIdx.x * SM_T + threadIdx.x;
+  if (j >= M) return;
+  int s = j;
+  if (highest) {
+    const float a = iou[3 * j], b = iou[3 * j + 1], c = iou[3 * j + 2];
+    s = 3 * j + (a >= b ? (a >= c ? 0 : 2) : (b >= c ? 1 : 2));
+  }
+  sel[j] = s;
+  iou_sel[j] = iou[s];
+  cnt[2 * j] = cnt[2 * j + 1] = 0;
+}
+
+__global__ void __launch_bounds__(SM_T) k_lr_count(int H, int W, float sy, float sx, int h_in, int w_in, const float* __restrict__ lowres,
+                                                   const int* __restrict__ sel, float thi, float tlo, int* __restrict__ cnt) {
+  __shared__ int red[2];
+  const int tid = threadIdx.x, j = blockIdx.y, npix = H * W;
+  if (tid < 2) red[tid] = 0;
+  __syncthreads();
+  const float* L = lowres + (size_t)sel[j] * LR * LR;
+  int ci = 0, cu = 0;
+  for (int p = blockIdx.x * SM_T + tid; p < npix; p += gridDim.x * SM_T) {
+    const int py = p / W, px = p - py * W;
+    const float v = lr_logit(L, lr_axis(py, sy, h_in), lr_axis(px, sx, w_in));
+    ci += v > thi;
+    cu += v > tlo;
+  }
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { ci += __shfl_xor(ci, d); cu += __shfl_xor(cu, d); }
+  if ((tid & 63) == 0) {
+    atomicAdd(&red[0], ci);
+    atomicAdd(&red[1], cu);
+  }
+  __syncthreads();
+  if (tid < 2 && red[tid]) atomicAdd(&cnt[2 * j + tid], red[tid]);
+}
+
+__global__ void __launch_bounds__(SM_T) k_lr_accum(int H, int W, float sy, float sx, int h_in, int w_in, int M, const float* __restrict__ lowres,
+                                                   const int* __restrict__ sel, const int* __restrict__ keep, float thr, int* __restrict__ count) {
+  const int p = blockIdx.x * SM_T + threadIdx.x;
+  if (p >= H * W) return;
+  const int py = p / W, px = p - py * W;
+  const LrAxis ay = lr_axis(py, sy, h_in), ax = lr_axis(px, sx, w_in);
+  int a = 0;
+  for (int j = 0; j < M; ++j)
+    if (keep[j]) a += lr_logit(lowres + (size_t)sel[j] * LR * LR, ay, ax) > thr;
+  if (a) count[p] += a;
+}
+
 // ---------------------------------------------------------------- 3. labels of the uncovered pixels
 constexpr int LB_W = 64, LB_H = 16;
 
@@ -525,6 +619,33 @@ extern "C" int hugs_sm_sfm_add(int N, int H, int W, const float* logits, const f
   HUGS_CHECK_LAUNCH("k_sfm_keep");
   k_sfm_accum<<<(nchunk + 3) / 4, SM_T, 0, s>>>(npix, nchunk, N, bits, keep, count);
   HUGS_CHECK_LAUNCH("k_sfm_accum");
+  return 0;
+}
+
+extern "C" int hugs_sm_sfm_add_lowres(int N, int H, int W, int h_in, int w_in, const float* lowres, const float* iou, float iou_thresh,
+                                      float mask_thr, float stab_off, float stab_thresh, int use_highest, int* count, int* keep, void* ws,
+                                      void* stream) {
+  SM_REQUIRE_HW("hugs_sm_sfm_add_lowres");
+  HUGS_REQUIRE(N >= 1 && N <= 16384, -2, "hugs_sm_sfm_add_lowres: %d prompts in one batch (1..16384)", N);
+  HUGS_REQUIRE(h_in >= 1 && h_in <= LR_UP && w_in >= 1 && w_in <= LR_UP, -2, "hugs_sm_sfm_add_lowres: input size %d x %d outside 1..%d",
+               h_in, w_in, LR_UP);
+  HUGS_REQUIRE(lowres && iou && count && keep && ws, -2, "hugs_sm_sfm_add_lowres: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  const int M = use_highest ? N : 3 * N, npix = H * W;
+  int* cnt = (int*)ws;
+  int* sel = cnt + 2 * M;
+  float* iou_sel = (float*)(sel + M);
+  const float thi = (float)((double)mask_thr + (double)stab_off), tlo = (float)((double)mask_thr - (double)stab_off);
+  const float sy = (float)h_in / (float)H, sx = (float)w_in / (float)W;
+  k_lr_select<<<(M + SM_T - 1) / SM_T, SM_T, 0, s>>>(M, use_highest, iou, sel, iou_sel, cnt);
+  HUGS_CHECK_LAUNCH("k_lr_select");
+  const int gx = (npix + SM_T * 8 - 1) / (SM_T * 8);
+  k_lr_count<<<dim3(gx, M), SM_T, 0, s>>>(H, W, sy, sx, h_in, w_in, lowres, sel, thi, tlo, cnt);
+  HUGS_CHECK_LAUNCH("k_lr_count");
+  k_sfm_keep<<<(M + SM_T - 1) / SM_T, SM_T, 0, s>>>(M, iou_sel, iou_thresh, stab_thresh, cnt, keep);
+  HUGS_CHECK_LAUNCH("k_sfm_keep");
+  k_lr_accum<<<(npix + SM_T - 1) / SM_T, SM_T, 0, s>>>(H, W, sy, sx, h_in, w_in, M, lowres, sel, keep, mask_thr, count);
+  HUGS_CHECK_LAUNCH("k_lr_accum");
   return 0;
 }
 

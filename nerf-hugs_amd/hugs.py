@@ -9,7 +9,10 @@ The caller brings, as device tensors,
 generate_static_mask returns what :269-407 compute; 'static_mask' is the content of static_masks/<name>.png, which
 internal/loaders.py reads back for `withmask` training.  Masks are [H,W] fp32 0/1 tensors like the reference's.
 
-Not here: SAM itself, the COLMAP point filtering / K-means that choose the prompts (:293-343), the visualisation panels.
+SamPointDecoder + SfmAccumulator.add_points run that SfM loop (:344-374) from the image embedding (csrc/hugs_samdecode.hip).
+
+Not here: SAM's image encoder and automatic mask generator, the COLMAP point filtering / K-means that choose the prompts
+(:293-343), the visualisation panels.
 intersect_threshold is a rational (numerator, denominator): the kernels compare inter * den >= num * area in integers."""
 import dataclasses
 import fractions
@@ -30,6 +33,8 @@ class SegmentConfig:
   residual_quantile_upper: float = 0.95
   smooth_kernel_size: int = 7
   erode_kernel_size: int = 5
+  sfm_seg_batch_size: int = 128
+  sfm_use_highest_iou: bool = True
 
 
 def check_image_size(height, width):
@@ -132,10 +137,145 @@ class SfmAccumulator:
     self.kept.append(keep)
     return self
 
+  def add_lowres(self, lowres, iou, input_size, mask_threshold=0.):
+    """:352-374 on the mask decoder's own output: lowres [N,3,256,256] logits and iou [N,3] (SamPointDecoder.predict),
+    input_size = (h_in, w_in) of the resized image inside the 1024 square.  The full-resolution logits are never materialised."""
+    h, w = self.count.shape
+    n = lowres.shape[0]
+    if tuple(lowres.shape) != (n, 3, 256, 256) or tuple(iou.shape) != (n, 3):
+      raise ValueError(f'lowres must be [N,3,256,256] and iou [N,3], got {tuple(lowres.shape)} and {tuple(iou.shape)}')
+    if n == 0:
+      return self
+    c = self.config
+    keep = torch.empty(n if c.sfm_use_highest_iou else 3 * n, dtype=torch.int32, device=self.count.device)
+    _lib.call('hugs_sm_sfm_add_lowres', n, h, w, int(input_size[0]), int(input_size[1]), lowres.to(torch.float32).contiguous(),
+              iou.to(torch.float32).contiguous(), c.sfm_pred_iou_thresh, mask_threshold, c.sfm_stability_score_offset,
+              c.sfm_stability_score_thresh, int(bool(c.sfm_use_highest_iou)), self.count, keep,
+              torch.empty(12 * n, dtype=torch.int32, device=self.count.device))
+    self.kept.append(keep)
+    return self
+
+  def add_points(self, decoder, points, labels=None):
+    """:344-374: the SfM feature points [N,P,2] (xy in original pixels) in batches of sfm_seg_batch_size through
+    decoder.predict and add_lowres.  decoder: a SamPointDecoder whose set_image has seen this image."""
+    if tuple(decoder.original_size) != tuple(self.count.shape):
+      raise ValueError(f'the decoder holds an image of {tuple(decoder.original_size)}, the accumulator is {tuple(self.count.shape)}')
+    step = int(self.config.sfm_seg_batch_size)
+    for i in range(0, points.shape[0], step):
+      lowres, iou = decoder.predict(points[i:i + step], None if labels is None else labels[i:i + step])
+      self.add_lowres(lowres, iou, decoder.input_size)
+    return self
+
   def mask(self):
     out = torch.empty(self.count.shape, dtype=torch.float32, device=self.count.device)
     _lib.call('hugs_sm_box', *self.count.shape, 1, self.count, None, None, 5, 1, 0, None, out)
     return out
+
+
+def _sam_keys():
+  """The segment_anything checkpoint keys SamPointDecoder reads, in the order the kernels' packed buffer holds them: each entry
+  is (key(s), packer); a linear weight [out,in] is stored transposed, [in][out]."""
+  pe, md = 'prompt_encoder.', 'mask_decoder.'
+  tr = md + 'transformer.'
+  flat = lambda t: t.reshape(-1)
+  lin_t = lambda t: t.t().reshape(-1)
+  cat_t = lambda *ts: torch.cat([t.t() for t in ts], 1).reshape(-1)
+  ks = [((pe + 'pe_layer.positional_encoding_gaussian_matrix',), flat)]
+  ks += [((k,), flat) for k in (pe + 'point_embeddings.0.weight', pe + 'point_embeddings.1.weight', pe + 'not_a_point_embed.weight',
+                                pe + 'no_mask_embed.weight', md + 'iou_token.weight', md + 'mask_tokens.weight')]
+
+  def t2i(a, norm):
+    return [((a + 'q_proj.weight',), lin_t), ((a + 'q_proj.bias',), flat), ((a + 'k_proj.weight', a + 'v_proj.weight'), cat_t),
+            ((a + 'k_proj.bias', a + 'v_proj.bias'), lambda k, v: torch.cat([k, v])),
+            ((a + 'k_proj.weight',), lambda k: torch.cat([k.t(), torch.zeros_like(k.t())], 1).reshape(-1)),      # keys of pos alone
+            ((a + 'out_proj.weight',), lin_t), ((a + 'out_proj.bias',), flat), ((norm + '.weight',), flat), ((norm + '.bias',), flat)]
+
+  for i in range(2):
+    l = f'{tr}layers.{i}.'
+    sa, ia = l + 'self_attn.', l + 'cross_attn_image_to_token.'
+    ks += [((sa + 'q_proj.weight', sa + 'k_proj.weight'), cat_t), ((sa + 'q_proj.bias', sa + 'k_proj.bias'), lambda q, k: torch.cat([q, k])),
+           ((sa + 'v_proj.weight',), lin_t), ((sa + 'v_proj.bias',), flat), ((sa + 'out_proj.weight',), lin_t), ((sa + 'out_proj.bias',), flat),
+           ((l + 'norm1.weight',), flat), ((l + 'norm1.bias',), flat)]
+    ks += t2i(l + 'cross_attn_token_to_image.', l + 'norm2')
+    ks += [((l + 'mlp.lin1.weight',), lin_t), ((l + 'mlp.lin1.bias',), flat), ((l + 'mlp.lin2.weight',), lin_t), ((l + 'mlp.lin2.bias',), flat),
+           ((l + 'norm3.weight',), flat), ((l + 'norm3.bias',), flat)]
+    for p in 'qkv':
+      ks += [((f'{ia}{p}_proj.weight',), lin_t), ((f'{ia}{p}_proj.bias',), flat)]
+    ks += [((ia + 'out_proj.weight',), lin_t), ((ia + 'out_proj.bias',), flat), ((l + 'norm4.weight',), flat), ((l + 'norm4.bias',), flat)]
+  ks += t2i(tr + 'final_attn_token_to_image.', tr + 'norm_final_attn')
+  up = md + 'output_upscaling.'
+  sub = lambda t: t.permute(0, 2, 3, 1).reshape(-1)             # ConvTranspose2d [Cin,Cout,2,2] -> [Cin][sub-pixel][Cout]
+  ks += [((up + '0.weight',), sub), ((up + '0.bias',), flat), ((up + '1.weight',), flat), ((up + '1.bias',), flat),
+         ((up + '3.weight',), sub), ((up + '3.bias',), flat)]
+  hy = [f'{md}output_hypernetworks_mlps.{m}.layers.' for m in range(4)]
+  for j in range(3):
+    ks += [(tuple(f'{h}{j}.weight' for h in hy), lambda *ts: torch.stack([t.t() for t in ts]).reshape(-1)),
+           (tuple(f'{h}{j}.bias' for h in hy), lambda *ts: torch.cat(ts))]
+  for j in range(3):
+    ks += [((f'{md}iou_prediction_head.layers.{j}.weight',), lin_t), ((f'{md}iou_prediction_head.layers.{j}.bias',), flat)]
+  return ks
+
+
+class SamPointDecoder:
+  """segment_anything's prompt encoder (points only) and mask decoder with multimask output as fp32 HIP kernels
+  (csrc/hugs_samdecode.hip): predictor.predict_torch(points, labels, multimask_output=True, return_logits=True) of
+  generate_static_mask.py:346-351 up to the low-resolution logits.  The ViT image encoder stays the caller's: set_image takes its
+  [256,64,64] embedding.  `weights`: a dict of tensors under the checkpoint's key names (all SAM sizes share this decoder);
+  ln_eps: the eps of the transformer's LayerNorms (1e-5 in segment_anything, 1e-6 in the transformers port)."""
+  MAX_POINTS = 10
+
+  def __init__(self, weights, device='cuda', ln_eps=1e-5):
+    keys = _sam_keys()
+    missing = [k for names, _ in keys for k in names if k not in weights]
+    if missing:
+      raise ValueError(f'SamPointDecoder: the weights lack {sorted(set(missing))}')
+    self.device, self.ln_eps = torch.device(device), float(ln_eps)
+    self.packed = torch.cat([pack(*(torch.as_tensor(weights[k]).detach().to('cpu', torch.float32) for k in names)).contiguous()
+                             for names, pack in keys]).to(self.device)
+    self.state = self.original_size = self.input_size = None
+
+  @classmethod
+  def from_checkpoint(cls, path, device='cuda', ln_eps=1e-5):
+    """A segment_anything checkpoint (sam_vit_*.pth), a local file; only the prompt encoder's and mask decoder's keys are read."""
+    return cls(torch.load(path, map_location='cpu', weights_only=True), device, ln_eps)
+
+  def set_image(self, embedding, original_size):
+    """embedding: the image encoder's output [256,64,64] (or [1,256,64,64]) for the image resized as ResizeLongestSide(1024)
+    does; original_size = (H, W).  Computes everything that depends on the image alone."""
+    if embedding.dim() == 4 and embedding.shape[0] == 1:
+      embedding = embedding[0]
+    if tuple(embedding.shape) != (256, 64, 64):
+      raise ValueError(f'embedding must be [256,64,64], got {tuple(embedding.shape)}')
+    h, w = (int(v) for v in original_size)
+    check_image_size(h, w)
+    scale = 1024. / max(h, w)
+    self.original_size, self.input_size = (h, w), (int(h * scale + 0.5), int(w * scale + 0.5))
+    self.state = torch.empty(_lib.call('hugs_sam_ws_bytes', 0, 1) // 4, dtype=torch.float32, device=self.device)
+    _lib.call('hugs_sam_set_image', self.packed, self.packed.numel(), embedding.to(self.device, torch.float32).contiguous(), self.state)
+    return self
+
+  def predict(self, points, labels=None):
+    """points [N,P,2]: xy in pixels of the original image; labels [N,P]: 1 foreground (the default), 0 background.
+    Returns (lowres [N,3,256,256] logits, iou [N,3])."""
+    if self.state is None:
+      raise ValueError('SamPointDecoder.predict before set_image')
+    if points.dim() != 3 or points.shape[-1] != 2 or not 1 <= points.shape[1] <= self.MAX_POINTS:
+      raise ValueError(f'points must be [N,P,2] with 1 <= P <= {self.MAX_POINTS}, got {tuple(points.shape)}')
+    n, p = points.shape[:2]
+    if labels is None:
+      labels = torch.ones((n, p), dtype=torch.int32, device=self.device)
+    if tuple(labels.shape) != (n, p):
+      raise ValueError(f'labels must be [{n},{p}], got {tuple(labels.shape)}')
+    (h, w), (h_in, w_in) = self.original_size, self.input_size
+    scale = torch.tensor([w_in / w, h_in / h], dtype=torch.float32, device=self.device)      # apply_coords
+    coords = (points.to(self.device, torch.float32) * scale).contiguous()
+    lowres = torch.empty((n, 3, 256, 256), dtype=torch.float32, device=self.device)
+    iou4 = torch.empty((n, 4), dtype=torch.float32, device=self.device)
+    if n:
+      ws = torch.empty(_lib.call('hugs_sam_ws_bytes', n, p) // 4, dtype=torch.float32, device=self.device)
+      _lib.call('hugs_sam_predict', n, p, coords, labels.to(self.device, torch.int32).contiguous(), self.packed, self.packed.numel(),
+                self.ln_eps, self.state, ws, lowres, iou4)
+    return lowres, iou4[:, 1:].contiguous()
 
 
 def label_uncovered(seg, num_segments=None):
