@@ -572,6 +572,18 @@ int hugs_sam_set_image(const float* packed, long long packed_floats, const float
 int hugs_sam_predict(int N, int P, const float* coords, const int* labels, const float* packed, long long packed_floats, float ln_eps,
                      const float* state, float* ws, float* lowres, float* iou4, void* stream);
 
+/* SAM's ViT image encoder (csrc/hugs_samencode.hip), fp32: Sam.preprocess + ImageEncoderViT, i.e. the model built at
+ * generate_static_mask.py:192 as predictor.set_image runs it at :338, after ResizeLongestSide(1024).apply_image.  D = embedding
+ * width (a multiple of 32, <= 1280), heads with D / heads 64 or 80, depth <= 64 blocks; the token grid is 64 x 64 (image side
+ * 1024, patch 16), windows are 14 x 14.  packed: the weights as nerf_hugs_amd.hugs.SamImageEncoder packs them (every matrix
+ * [in][out]; the length is checked).  global_flags: HOST array of depth ints, 1 = global attention (rel-pos tables of 127 rows),
+ * 0 = windowed (27 rows).  image: [h_in, w_in, 3] RGB in 0..255, uint8 (image_u8 1) or float32 (0), h_in, w_in <= 1024: normalised
+ * and zero-padded to 1024 x 1024 at the bottom and right by the patch-embedding loader.  ws: hugs_sam_enc_ws_bytes(D, depth, heads)
+ * bytes; out [256,64,64], what hugs_sam_set_image takes.  packed, ws, out 16-byte aligned.  Deterministic; no host synchronisation. */
+long long hugs_sam_enc_ws_bytes(int D, int depth, int heads);
+int hugs_sam_enc_encode(int D, int depth, int heads, const float* packed, long long packed_floats, const int* global_flags,
+                        const void* image, int image_u8, int h_in, int w_in, float* ws, float* out, void* stream);
+
 /* test/bench forms of hugs_gemm_nt / hugs_gemm_tn with an explicit kernel selection (a call argument: no process
  * state): tile_mode 0 = the default choice (what the plain entry points use), 1 = force the 128x128-tile kernels,
  * 3 = the 256x128 NT kernel where a 256x256 one would be chosen, 5 = 256x256 without the persistent form */

@@ -81,6 +81,8 @@ _PROTOS = {
     'hugs_sam_ws_bytes': 'ii',
     'hugs_sam_set_image': 'pqpps',
     'hugs_sam_predict': 'iipppqfpppps',
+    'hugs_sam_enc_ws_bytes': 'iii',
+    'hugs_sam_enc_encode': 'iiipqppiiipps',
     'hugs_sm_label': 'iiipps',
     'hugs_sm_label_hist': 'iiippps',
     'hugs_sm_select_erode': 'iippiiiips',
@@ -194,6 +196,7 @@ class _Lib:
     self.cdll.hugs_lpips_alex_ws_bytes.restype = ctypes.c_longlong
     self.cdll.hugs_sm_ws_bytes.restype = ctypes.c_longlong
     self.cdll.hugs_sam_ws_bytes.restype = ctypes.c_longlong
+    self.cdll.hugs_sam_enc_ws_bytes.restype = ctypes.c_longlong
 
   def declare(self, name, sig):
     _PROTOS[name] = sig

@@ -9,9 +9,10 @@ The caller brings, as device tensors,
 generate_static_mask returns what :269-407 compute; 'static_mask' is the content of static_masks/<name>.png, which
 internal/loaders.py reads back for `withmask` training.  Masks are [H,W] fp32 0/1 tensors like the reference's.
 
-SamPointDecoder + SfmAccumulator.add_points run that SfM loop (:344-374) from the image embedding (csrc/hugs_samdecode.hip).
+SamPointDecoder + SfmAccumulator.add_points run that SfM loop (:344-374) from the image embedding (csrc/hugs_samdecode.hip);
+SamImageEncoder computes that embedding from the resized image (:338, csrc/hugs_samencode.hip).
 
-Not here: SAM's image encoder and automatic mask generator, the COLMAP point filtering / K-means that choose the prompts
+Not here: SAM's automatic mask generator, box and mask prompts, the PIL resize, the COLMAP point filtering / K-means that choose the prompts
 (:293-343), the visualisation panels.
 intersect_threshold is a rational (numerator, denominator): the kernels compare inter * den >= num * area in integers."""
 import dataclasses
@@ -216,11 +217,107 @@ def _sam_keys():
   return ks
 
 
+_ENC_GRID, _ENC_WINDOW = 64, 14
+
+
+def _sam_enc_config(weights):
+  """(D, depth, heads, global flags) read from the image_encoder.* tensors; ValueError naming the key for an unsupported shape."""
+  ie = 'image_encoder.'
+  nums = [int(k[len(ie) + 7:].split('.')[0]) for k in weights if k.startswith(ie + 'blocks.')]
+  depth = max(nums) + 1 if nums else 0
+  need = [ie + 'pos_embed'] + [f'{ie}blocks.{i}.attn.rel_pos_{a}' for i in range(depth) for a in 'hw']
+  missing = [k for k in need if k not in weights]
+  if missing or not depth:
+    raise ValueError(f'SamImageEncoder: the weights lack {sorted(missing) or [ie + "blocks.0.*"]}')
+  pos = weights[ie + 'pos_embed']
+  if pos.dim() != 4 or tuple(pos.shape[:3]) != (1, _ENC_GRID, _ENC_GRID) or pos.shape[-1] % 32:
+    raise ValueError(f'SamImageEncoder: {ie}pos_embed must be [1,64,64,D] with D a multiple of 32, got {tuple(pos.shape)}')
+  dim, hd = int(pos.shape[-1]), int(weights[ie + 'blocks.0.attn.rel_pos_h'].shape[-1])
+  if hd not in (64, 80) or dim % hd:
+    raise ValueError(f'SamImageEncoder: {ie}blocks.0.attn.rel_pos_h has head size {hd} (64 or 80, dividing D = {dim})')
+  flags = []
+  for i in range(depth):
+    rows = {a: tuple(weights[f'{ie}blocks.{i}.attn.rel_pos_{a}'].shape) for a in 'hw'}
+    for a, shape in rows.items():      # no rel-pos interpolation: the tables have 2 G - 1 rows for G = 64 (global) or 14 (window)
+      if shape not in ((2 * _ENC_GRID - 1, hd), (2 * _ENC_WINDOW - 1, hd)) or shape != rows['h']:
+        raise ValueError(f'SamImageEncoder: {ie}blocks.{i}.attn.rel_pos_{a} must be [127,{hd}] or [27,{hd}] like rel_pos_h, got {shape}')
+    flags.append(int(rows['h'][0] == 2 * _ENC_GRID - 1))
+  return dim, depth, dim // hd, flags
+
+
+def _sam_enc_keys(depth, flags):
+  """The image_encoder.* keys SamImageEncoder reads, in the order the kernels' packed buffer holds them (as _sam_keys)."""
+  ie = 'image_encoder.'
+  flat = lambda t: t.reshape(-1)
+  lin_t = lambda t: t.t().reshape(-1)
+  conv_t = lambda t: t.permute(2, 3, 1, 0).reshape(-1)      # [out,in,kh,kw] -> [(kh, kw, in)][out]: the loaders' K order
+  ks = [((ie + 'patch_embed.proj.weight',), conv_t), ((ie + 'patch_embed.proj.bias',), flat), ((ie + 'pos_embed',), flat)]
+  for i in range(depth):
+    b = f'{ie}blocks.{i}.'
+    width, off = (256, 128) if flags[i] else (64, 32)
+
+    def rel(h, w, width=width, off=off):      # [hd][width]: rel_pos_h^T from column 0, rel_pos_w^T from column off, zeros between
+      out = torch.zeros(h.shape[1], width)
+      out[:, :h.shape[0]], out[:, off:off + w.shape[0]] = h.t(), w.t()
+      return out.reshape(-1)
+
+    ks += [((b + 'norm1.weight',), flat), ((b + 'norm1.bias',), flat), ((b + 'attn.qkv.weight',), lin_t), ((b + 'attn.qkv.bias',), flat),
+           ((b + 'attn.rel_pos_h', b + 'attn.rel_pos_w'), rel), ((b + 'attn.proj.weight',), lin_t), ((b + 'attn.proj.bias',), flat),
+           ((b + 'norm2.weight',), flat), ((b + 'norm2.bias',), flat), ((b + 'mlp.lin1.weight',), lin_t), ((b + 'mlp.lin1.bias',), flat),
+           ((b + 'mlp.lin2.weight',), lin_t), ((b + 'mlp.lin2.bias',), flat)]
+  nk = ie + 'neck.'
+  ks += [((nk + '0.weight',), conv_t), ((nk + '1.weight',), flat), ((nk + '1.bias',), flat),
+         ((nk + '2.weight',), conv_t), ((nk + '3.weight',), flat), ((nk + '3.bias',), flat)]
+  return ks
+
+
+class SamImageEncoder:
+  """segment_anything's Sam.preprocess + ImageEncoderViT as fp32 HIP kernels (csrc/hugs_samencode.hip): the
+  predictor.set_image(sam_image) of generate_static_mask.py:338 after ResizeLongestSide(1024).apply_image (the PIL resize is
+  host image I/O and stays the caller's).  `weights`: a dict of tensors under the checkpoint's key names; width, depth, heads
+  and which blocks attend globally are read from the image_encoder.* shapes (vit_b, vit_l and vit_h all qualify)."""
+
+  def __init__(self, weights, device='cuda'):
+    import ctypes
+    self.dim, self.depth, self.heads, flags = _sam_enc_config(weights)
+    keys = _sam_enc_keys(self.depth, flags)
+    missing = [k for names, _ in keys for k in names if k not in weights]
+    if missing:
+      raise ValueError(f'SamImageEncoder: the weights lack {sorted(set(missing))}')
+    self.device = torch.device(device)
+    self.global_flags = (ctypes.c_int * self.depth)(*flags)      # (a host array: the library reads it while enqueueing)
+    self.packed = torch.cat([pack(*(torch.as_tensor(weights[k]).detach().to('cpu', torch.float32) for k in names)).contiguous()
+                             for names, pack in keys]).to(self.device)
+    size = _lib.call('hugs_sam_enc_ws_bytes', self.dim, self.depth, self.heads)
+    if size < 0:
+      raise ValueError(_lib.lib().cdll.hugs_last_error().decode())
+    self.ws = torch.empty(size // 4, dtype=torch.float32, device=self.device)
+
+  @classmethod
+  def from_checkpoint(cls, path, device='cuda'):
+    """A segment_anything checkpoint (sam_vit_*.pth), a local file; only the image encoder's keys are read."""
+    return cls(torch.load(path, map_location='cpu', weights_only=True), device)
+
+  def encode(self, image):
+    """image [h_in, w_in, 3]: RGB in 0..255, uint8 or float32, max(h_in, w_in) <= 1024.  Returns the embedding [256,64,64] fp32."""
+    import ctypes
+    if image.dim() != 3 or image.shape[-1] != 3 or not 1 <= max(image.shape[:2]) <= 1024:
+      raise ValueError(f'image must be [h,w,3] with h, w <= 1024, got {tuple(image.shape)}')
+    if image.dtype != torch.uint8:
+      image = image.to(torch.float32)
+    image = image.to(self.device).contiguous()
+    out = torch.empty((256, _ENC_GRID, _ENC_GRID), dtype=torch.float32, device=self.device)
+    _lib.call('hugs_sam_enc_encode', self.dim, self.depth, self.heads, self.packed, self.packed.numel(),
+              ctypes.addressof(self.global_flags), image, int(image.dtype == torch.uint8), image.shape[0], image.shape[1], self.ws, out)
+    return out
+
+
 class SamPointDecoder:
   """segment_anything's prompt encoder (points only) and mask decoder with multimask output as fp32 HIP kernels
   (csrc/hugs_samdecode.hip): predictor.predict_torch(points, labels, multimask_output=True, return_logits=True) of
-  generate_static_mask.py:346-351 up to the low-resolution logits.  The ViT image encoder stays the caller's: set_image takes its
-  [256,64,64] embedding.  `weights`: a dict of tensors under the checkpoint's key names (all SAM sizes share this decoder);
+  generate_static_mask.py:346-351 up to the low-resolution logits.  set_image takes the ViT image encoder's [256,64,64]
+  embedding, from SamImageEncoder.encode (set_image_from does both) or from a stack of the caller's.  `weights`: a dict of tensors
+  under the checkpoint's key names (all SAM sizes share this decoder);
   ln_eps: the eps of the transformer's LayerNorms (1e-5 in segment_anything, 1e-6 in the transformers port)."""
   MAX_POINTS = 10
 
@@ -253,6 +350,10 @@ class SamPointDecoder:
     self.state = torch.empty(_lib.call('hugs_sam_ws_bytes', 0, 1) // 4, dtype=torch.float32, device=self.device)
     _lib.call('hugs_sam_set_image', self.packed, self.packed.numel(), embedding.to(self.device, torch.float32).contiguous(), self.state)
     return self
+
+  def set_image_from(self, encoder, image, original_size):
+    """set_image(encoder.encode(image), original_size): encoder a SamImageEncoder, image the resized RGB image [h_in,w_in,3]."""
+    return self.set_image(encoder.encode(image), original_size)
 
   def predict(self, points, labels=None):
     """points [N,P,2]: xy in pixels of the original image; labels [N,P]: 1 foreground (the default), 0 background.
