@@ -584,6 +584,51 @@ long long hugs_sam_enc_ws_bytes(int D, int depth, int heads);
 int hugs_sam_enc_encode(int D, int depth, int heads, const float* packed, long long packed_floats, const int* global_flags,
                         const void* image, int image_u8, int h_in, int w_in, float* ws, float* out, void* stream);
 
+/* SAM's automatic mask generator around the encoder and the decoder (csrc/hugs_samamg.hip): what
+ * SamAutomaticMaskGenerator.generate (generate_static_mask.py:193-201, :237) does with the decoder's outputs, and the painting of
+ * :237-242.  Images are H x W with 3 <= H, W <= 4096 and H * W <= 2^24; a mask set holds up to 65536 masks, bit-packed as
+ * [K, H, ceil(W/64)] 64-bit words, bit l of word c of a row = pixel 64 c + l.  Boxes are int32 (x0, y0, x1, y1) with inclusive maxima
+ * (batched_mask_to_box; zeros for an empty mask).  Every decision is integer arithmetic or one correctly rounded fp32 quotient;
+ * deterministic; no entry synchronises with the host.
+ * hugs_amg_ws_bytes: what 0: hugs_amg_candidates for n prompts on an H x W crop; 1: hugs_amg_nms for n boxes; 2:
+ *   hugs_amg_small_regions with chunks of n masks.
+ * hugs_amg_candidates: _process_batch behind :237 for lowres [N,3,256,256], iou [N,3] of one crop (cx0, cy0, cx1, cy1), resized to
+ *   h_in x w_in, and the prompts' points [N,2] in crop pixels.  Candidate 3 n + j is kept when iou > iou_thresh (skipped when <= 0),
+ *   #(logit > thr + off) / #(logit > thr - off) >= stab_thresh (skipped when <= 0) and its box is not near a crop edge that is not
+ *   an image edge (is_box_near_crop_edge, atol 20); logits are postprocess_masks per output pixel as in hugs_sm_sfm_add_lowres.
+ *   The kept ones take the slots base, base + 1, ... in candidate order (base + 3 N <= cap): plane words at the crop's offset
+ *   (uncrop_masks), box and point moved to image coordinates, iou, stability, area = #(logit > thr), the crop box; *nkept = count.
+ * hugs_amg_pack: [K,H,W] byte planes (nonzero = set) -> bit planes, or back (unpack != 0).
+ * hugs_amg_mask_stats: boxes [K,4] and areas [K] (popcounts) of bit planes.
+ * hugs_amg_rank: rank[i] = #{j : key_j > key_i or (key_j == key_i and j < i)} for fp32 (keys_int 0) or int32 keys -- the stable
+ *   descending order sorted(..., reverse=True) of :237 and the NMS rounds use -- and order[rank[i]] = i.
+ * hugs_amg_nms: torchvision.ops.nms (the batched_nms calls of the generator) on int32 boxes taken in the order `order`: box b is
+ *   dropped when an earlier survivor a has inter / (area_a + area_b - inter) > iou_threshold (fp32, IEEE division; 0/0 keeps).
+ *   keep[0 .. *nkeep) = the survivors' indices in that order, what MaskData.filter(keep) reorders by.
+ * hugs_amg_gather: MaskData.filter for one array of K rows of `row` 4-byte words: dst row j = src row keep[j] (j < *nkeep), or
+ *   the row of alt where alt != NULL and sel[keep[j]] != 0 (postprocess_small_regions' replacement of changed masks).
+ * hugs_amg_small_regions: remove_small_regions(mode "holes") then ("islands") on every mask, 8-connected: background components
+ *   under min_area pixels are set, then foreground components under min_area are cleared -- when all are, the largest stays (ties:
+ *   the one whose first pixel in raster order comes first).  clean = the result; changed[k] = 1 when a pass found a region under
+ *   min_area (segment_anything's flag: also set when the only island is small and stays).  boxes: the masks' boxes (the work is
+ *   confined to them); `chunk` masks are labelled at a time in ws.
+ * hugs_amg_paint: :237-242 after the sort.  order[r] = the mask of rank r (hugs_amg_rank by area); seg[H,W] = the largest r whose
+ *   mask covers the pixel, -1 where none does. */
+long long hugs_amg_ws_bytes(int what, int H, int W, int n);
+int hugs_amg_candidates(int N, int H, int W, int cx0, int cy0, int cx1, int cy1, int h_in, int w_in, const float* lowres,
+                        const float* iou, const float* points, float iou_thresh, float stab_thresh, float stab_off, float mask_thr,
+                        int base, int cap, void* masks, int* boxes, float* iou_out, float* stab_out, int* area, float* points_out,
+                        int* crop_out, int* nkept, void* ws, void* stream);
+int hugs_amg_pack(int K, int H, int W, int unpack, void* planes, void* masks, void* stream);
+int hugs_amg_mask_stats(int K, int H, int W, const void* masks, int* boxes, int* area, void* stream);
+int hugs_amg_rank(int K, const void* keys, int keys_int, int* rank, int* order, void* stream);
+int hugs_amg_nms(int K, const int* boxes, const int* order, float iou_threshold, int* keep, int* nkeep, void* ws, void* stream);
+int hugs_amg_gather(int K, long long row, const int* keep, const int* nkeep, const int* sel, const void* src, const void* alt, void* dst,
+                    void* stream);
+int hugs_amg_small_regions(int K, int H, int W, int min_area, const void* masks, const int* boxes, void* clean, int* changed, int chunk,
+                           void* ws, void* stream);
+int hugs_amg_paint(int S, int H, int W, const void* masks, const int* boxes, const int* order, int* seg, void* stream);
+
 /* test/bench forms of hugs_gemm_nt / hugs_gemm_tn with an explicit kernel selection (a call argument: no process
  * state): tile_mode 0 = the default choice (what the plain entry points use), 1 = force the 128x128-tile kernels,
  * 3 = the 256x128 NT kernel where a 256x256 one would be chosen, 5 = 256x256 without the persistent form */

@@ -83,6 +83,15 @@ _PROTOS = {
     'hugs_sam_predict': 'iipppqfpppps',
     'hugs_sam_enc_ws_bytes': 'iii',
     'hugs_sam_enc_encode': 'iiipqppiiipps',
+    'hugs_amg_ws_bytes': 'iiii',
+    'hugs_amg_candidates': 'iiiiiiiiipppffffiippppppppps',
+    'hugs_amg_pack': 'iiiipps',
+    'hugs_amg_mask_stats': 'iiippps',
+    'hugs_amg_rank': 'ipipps',
+    'hugs_amg_nms': 'ippfppps',
+    'hugs_amg_gather': 'iqpppppps',
+    'hugs_amg_small_regions': 'iiiippppips',
+    'hugs_amg_paint': 'iiipppps',
     'hugs_sm_label': 'iiipps',
     'hugs_sm_label_hist': 'iiippps',
     'hugs_sm_select_erode': 'iippiiiips',
@@ -197,6 +206,7 @@ class _Lib:
     self.cdll.hugs_sm_ws_bytes.restype = ctypes.c_longlong
     self.cdll.hugs_sam_ws_bytes.restype = ctypes.c_longlong
     self.cdll.hugs_sam_enc_ws_bytes.restype = ctypes.c_longlong
+    self.cdll.hugs_amg_ws_bytes.restype = ctypes.c_longlong
 
   def declare(self, name, sig):
     _PROTOS[name] = sig

@@ -12,8 +12,11 @@ internal/loaders.py reads back for `withmask` training.  Masks are [H,W] fp32 0/
 SamPointDecoder + SfmAccumulator.add_points run that SfM loop (:344-374) from the image embedding (csrc/hugs_samdecode.hip);
 SamImageEncoder computes that embedding from the resized image (:338, csrc/hugs_samencode.hip).
 
-Not here: SAM's automatic mask generator, box and mask prompts, the PIL resize, the COLMAP point filtering / K-means that choose the prompts
-(:293-343), the visualisation panels.
+SamMaskGenerator computes `seg` itself: segment_anything's SamAutomaticMaskGenerator around those two (:193-201, :237-242;
+csrc/hugs_samamg.hip), with its masks bit-packed on the device in a MaskSet.
+
+Not here: box and mask prompts, RLE output, the COLMAP point filtering / K-means that choose the prompts (:293-343), the
+visualisation panels.  The PIL resize of the generator's crops is host image I/O (a replaceable callable).
 intersect_threshold is a rational (numerator, denominator): the kernels compare inter * den >= num * area in integers."""
 import dataclasses
 import fractions
@@ -442,6 +445,283 @@ def generate_static_mask(pred, gt, seg, sfm=None, config=None, num_segments=None
   static = _select_erode(smoothed, labels, num_segments, (1, 2), ke)
   return {'residual': residual, 'residual_mask_base': base, 'residual_mask_upper': upper, 'sfm_mask': sfm_mask,
           'sfm_residual_mask': combined, 'labels': labels, 'static_mask': static}
+
+
+@dataclasses.dataclass
+class SamAmgConfig:
+  """SamAutomaticMaskGenerator's fields: HuGS's values (generate_static_mask.py:19-36) where HuGS sets them, segment_anything's
+  defaults for the rest."""
+  points_per_side: int = 64
+  pred_iou_thresh: float = 0.8
+  stability_score_thresh: float = 0.9
+  crop_n_layers: int = 1
+  crop_n_points_downscale_factor: int = 2
+  min_mask_region_area: int = 50
+  points_per_batch: int = 64
+  stability_score_offset: float = 1.0
+  box_nms_thresh: float = 0.7
+  crop_nms_thresh: float = 0.7
+  crop_overlap_ratio: float = 512 / 1500
+
+
+def amg_crop_boxes(size, n_layers=1, overlap_ratio=512 / 1500):
+  """segment_anything's generate_crop_boxes for an image of size (H, W): ([x0, y0, x1, y1] per crop, the whole image first,
+  and each crop's layer index)."""
+  import itertools
+  import math
+  h, w = (int(v) for v in size)
+  boxes, layers = [[0, 0, w, h]], [0]
+  for layer in range(int(n_layers)):
+    n = 2**(layer + 1)
+    overlap = int(overlap_ratio * min(h, w) * (2 / n))
+    crop_w, crop_h = (int(math.ceil((overlap * (n - 1) + side) / n)) for side in (w, h))
+    xs, ys = ([int((c - overlap) * i) for i in range(n)] for c in (crop_w, crop_h))
+    for x0, y0 in itertools.product(xs, ys):
+      boxes.append([x0, y0, min(x0 + crop_w, w), min(y0 + crop_h, h)])
+      layers.append(layer + 1)
+  return boxes, layers
+
+
+def amg_point_grids(points_per_side=64, n_layers=1, downscale=2):
+  """segment_anything's build_all_layer_point_grids: per layer an [n * n, 2] float64 numpy array of (x, y) in [0, 1], row-major."""
+  import numpy as np
+  grids = []
+  for layer in range(int(n_layers) + 1):
+    n = int(points_per_side / (downscale**layer))
+    offset = 1 / (2 * n)
+    side = np.linspace(offset, 1 - offset, n)
+    grids.append(np.stack([np.tile(side[None, :], (n, 1)), np.tile(side[:, None], (1, n))], -1).reshape(-1, 2))
+  return grids
+
+
+def _amg_ws(what, height, width, n, device):
+  size = _lib.call('hugs_amg_ws_bytes', what, height, width, n)
+  if size < 0:
+    raise ValueError(_lib.lib().cdll.hugs_last_error().decode())
+  return torch.empty(size // 8 + 1, dtype=torch.int64, device=device)
+
+
+def stable_rank(keys):
+  """keys [K] float32 or int32 on the device -> (rank, order) int32: rank[i] = #{j : key_j > key_i or (key_j == key_i and j < i)},
+  the stable descending order (the lower index first among equals), and its inverse order[rank[i]] = i."""
+  if keys.dim() != 1 or keys.dtype not in (torch.float32, torch.int32):
+    raise ValueError(f'keys must be [K] float32 or int32, got {tuple(keys.shape)} {keys.dtype}')
+  keys = keys.contiguous()
+  rank, order = torch.empty_like(keys, dtype=torch.int32), torch.empty_like(keys, dtype=torch.int32)
+  if len(keys):
+    _lib.call('hugs_amg_rank', len(keys), keys, int(keys.dtype == torch.int32), rank, order)
+  return rank, order
+
+
+def box_nms(boxes, scores, iou_threshold):
+  """torchvision.ops.nms for integer boxes [K,4] (x0, y0, x1, y1 <= 4096) with a stable score order: returns (keep, count), keep
+  [K] int32 holding the surviving indices in descending score order in its first `count` (a device int32 [1]) entries."""
+  boxes = boxes.to(torch.int32).contiguous()
+  k = boxes.shape[0]
+  keep, count = torch.empty(k, dtype=torch.int32, device=boxes.device), torch.zeros(1, dtype=torch.int32, device=boxes.device)
+  if k:
+    _, order = stable_rank(scores)
+    _lib.call('hugs_amg_nms', k, boxes, order, iou_threshold, keep, count, _amg_ws(1, 3, 3, k, boxes.device))
+  return keep, count
+
+
+class MaskSet:
+  """SamAutomaticMaskGenerator's MaskData on the device.  masks_bits [K,H,ceil(W/64)] int64: bit l of word c of a row is pixel
+  64 c + l; boxes [K,4] int32 (x0, y0, x1, y1 with inclusive maxima, batched_mask_to_box); iou, stability [K] float32; area [K]
+  int32; points [K,2] float32; crop_boxes [K,4] int32.  The attributes are views of the first `len` rows of growing buffers."""
+  FIELDS = {'masks_bits': (torch.int64, None), 'boxes': (torch.int32, 4), 'iou': (torch.float32, 0), 'stability': (torch.float32, 0),
+            'area': (torch.int32, 0), 'points': (torch.float32, 2), 'crop_boxes': (torch.int32, 4)}
+
+  def __init__(self, height, width, capacity=0, device='cuda'):
+    check_image_size(height, width)
+    if max(height, width) > 4096:
+      raise ValueError(f'MaskSet: image {height} x {width} has a side over 4096')
+    self.height, self.width, self.words, self.device, self.len = int(height), int(width), (int(width) + 63) // 64, torch.device(device), 0
+    self._buf = {name: self._new(name, 0) for name in self.FIELDS}
+    self.reserve(capacity)
+
+  def _new(self, name, rows):
+    dtype, cols = self.FIELDS[name]
+    shape = (rows, self.height, self.words) if cols is None else ((rows, cols) if cols else (rows,))
+    return torch.zeros(shape, dtype=dtype, device=self.device)
+
+  def __len__(self):
+    return self.len
+
+  def __getattr__(self, name):
+    if name in MaskSet.FIELDS:
+      return self._buf[name][:self.len]
+    raise AttributeError(name)
+
+  def reserve(self, rows):
+    """Room for `rows` masks; the buffers at least double when they grow."""
+    have = self._buf['iou'].shape[0]
+    if rows > have:
+      for name, old in self._buf.items():
+        self._buf[name] = self._new(name, max(rows, 2 * have))
+        self._buf[name][:self.len] = old[:self.len]
+    return self
+
+  @classmethod
+  def from_masks(cls, masks, iou=None, stability=None, points=None, crop_boxes=None):
+    """masks: [K,H,W] bool on the device; boxes and areas are computed, the other fields default to zeros (crop_boxes: the image)."""
+    if masks.dim() != 3 or masks.dtype != torch.bool:
+      raise ValueError(f'masks must be [K,H,W] bool, got {tuple(masks.shape)} {masks.dtype}')
+    k, h, w = masks.shape
+    self = cls(h, w, k, masks.device)
+    self.len = k
+    if k:
+      _lib.call('hugs_amg_pack', k, h, w, 0, masks.contiguous(), self._buf['masks_bits'])
+      _lib.call('hugs_amg_mask_stats', k, h, w, self._buf['masks_bits'], self._buf['boxes'], self._buf['area'])
+      self._buf['crop_boxes'][:] = torch.tensor([0, 0, w, h], dtype=torch.int32, device=masks.device)
+      for name, value in (('iou', iou), ('stability', stability), ('points', points), ('crop_boxes', crop_boxes)):
+        if value is not None:
+          self._buf[name][:k] = value.to(masks.device)
+    return self
+
+  def to_masks(self):
+    out = torch.empty((self.len, self.height, self.width), dtype=torch.bool, device=self.device)
+    if self.len:
+      _lib.call('hugs_amg_pack', self.len, self.height, self.width, 1, out, self._buf['masks_bits'])
+    return out
+
+  def _filter(self, start, keep, count, changed=None, alt=None):
+    """MaskData.filter(keep) on rows start..len: row start + j becomes row start + keep[j], taken from alt[name] where changed."""
+    k = self.len - start
+    for name, buf in self._buf.items():
+      src = buf[start:self.len]
+      dst = torch.empty_like(src)
+      _lib.call('hugs_amg_gather', k, src[0].numel() * src.element_size() // 4, keep, count, changed, src,
+                alt.get(name) if alt else None, dst)
+      buf[start:self.len] = dst
+    self.len = start + int(count)
+
+  def nms(self, scores, iou_threshold, start=0):
+    """batched_nms + MaskData.filter on the masks from `start` on (scores [len - start]): the survivors, in descending score
+    order (stable), replace them.  Returns their former indices relative to `start`."""
+    if self.len == start:
+      return torch.empty(0, dtype=torch.int32, device=self.device)
+    keep, count = box_nms(self._buf['boxes'][start:self.len], scores, iou_threshold)
+    self._filter(start, keep, count)
+    return keep[:self.len - start]
+
+  def clean_small_regions(self, min_area, max_bytes=1 << 28):
+    """remove_small_regions(mode='holes') then (mode='islands') on every mask.  Returns (a MaskSet of the cleaned masks with their
+    boxes and areas, changed [K] int32: 1 where a pass found a region under min_area).  The union-find workspace stays under
+    max_bytes by running the masks in chunks."""
+    out = MaskSet(self.height, self.width, self.len, self.device)
+    out.len = k = self.len
+    changed = torch.zeros(k, dtype=torch.int32, device=self.device)
+    if k:
+      for name in ('iou', 'stability', 'points', 'crop_boxes'):
+        out._buf[name][:k] = self._buf[name][:k]
+      chunk = max(1, min(k, max_bytes // (8 * (self.height * self.width + 6))))
+      _lib.call('hugs_amg_small_regions', k, self.height, self.width, int(min_area), self._buf['masks_bits'], self._buf['boxes'],
+                out._buf['masks_bits'], changed, chunk, _amg_ws(2, self.height, self.width, chunk, self.device))
+      _lib.call('hugs_amg_mask_stats', k, self.height, self.width, out._buf['masks_bits'], out._buf['boxes'], out._buf['area'])
+    return out, changed
+
+  def remove_small_regions(self, min_area, nms_thresh):
+    """postprocess_small_regions: clean every mask, NMS on the cleaned boxes with score 1 - changed, and the survivors that
+    changed take their cleaned mask, box and area.  Returns the survivors' former indices."""
+    if not self.len:
+      return torch.empty(0, dtype=torch.int32, device=self.device)
+    clean, changed = self.clean_small_regions(min_area)
+    keep, count = box_nms(clean.boxes, 1 - changed, nms_thresh)
+    self._filter(0, keep, count, changed, {n: clean._buf[n][:self.len] for n in ('masks_bits', 'boxes', 'area')})
+    return keep[:self.len]
+
+  def label_map(self):
+    """generate_static_mask.py:237-242: (seg [H,W] int32, S): seg = the rank by area (descending, stable) of the smallest mask
+    covering the pixel, -1 where none does; the `seg`, `num_segments` of generate_static_mask."""
+    seg = torch.empty((self.height, self.width), dtype=torch.int32, device=self.device)
+    boxes, area = torch.empty((self.len, 4), dtype=torch.int32, device=self.device), torch.empty(self.len, dtype=torch.int32, device=self.device)
+    if self.len:
+      _lib.call('hugs_amg_mask_stats', self.len, self.height, self.width, self._buf['masks_bits'], boxes, area)
+    _, order = stable_rank(area)
+    _lib.call('hugs_amg_paint', self.len, self.height, self.width, self._buf['masks_bits'], boxes, order, seg)
+    return seg, self.len
+
+
+def _pil_resize(image, size):
+  """ResizeLongestSide.apply_image's resize: Pillow bilinear to size = (h, w)."""
+  import numpy as np
+  from PIL import Image
+  return np.array(Image.fromarray(image).resize((size[1], size[0]), Image.BILINEAR))
+
+
+class SamMaskGenerator:
+  """segment_anything's SamAutomaticMaskGenerator (binary masks) on a SamImageEncoder and a SamPointDecoder:
+  generate_static_mask.py:193-201 and the generate() of :237.  resize(crop [h,w,3] uint8 numpy, (h_in, w_in)) -> [h_in,w_in,3] uint8
+  numpy is host image I/O; the default is Pillow's bilinear resize, what ResizeLongestSide.apply_image does."""
+
+  def __init__(self, encoder, decoder, config=None, resize=None):
+    self.encoder, self.decoder = encoder, decoder
+    self.config = config if config is not None else SamAmgConfig()
+    self.resize = resize if resize is not None else _pil_resize
+
+  @classmethod
+  def from_checkpoint(cls, path, config=None, device='cuda', resize=None):
+    """A segment_anything checkpoint (sam_vit_*.pth), a local file: the encoder and the decoder are built from the one dict."""
+    weights = torch.load(path, map_location='cpu', weights_only=True)
+    return cls(SamImageEncoder(weights, device), SamPointDecoder(weights, device), config, resize)
+
+  def add_candidates(self, mask_set, lowres, iou, points, crop_box, mask_threshold=0.):
+    """_process_batch after the decoder: lowres [N,3,256,256], iou [N,3] (SamPointDecoder.predict for the crop), points [N,2] xy in
+    crop pixels, crop_box (x0, y0, x1, y1).  Appends the kept candidates to mask_set in candidate order; returns how many."""
+    n = lowres.shape[0]
+    if tuple(lowres.shape) != (n, 3, 256, 256) or tuple(iou.shape) != (n, 3) or tuple(points.shape) != (n, 2):
+      raise ValueError(f'lowres [N,3,256,256], iou [N,3], points [N,2]: got {tuple(lowres.shape)}, {tuple(iou.shape)}, {tuple(points.shape)}')
+    if n == 0:
+      return 0
+    c, m = self.config, mask_set
+    x0, y0, x1, y1 = (int(v) for v in crop_box)
+    scale = 1024. / max(y1 - y0, x1 - x0)
+    h_in, w_in = int((y1 - y0) * scale + 0.5), int((x1 - x0) * scale + 0.5)
+    m.reserve(m.len + 3 * n)
+    b, kept = m._buf, torch.zeros(1, dtype=torch.int32, device=m.device)
+    _lib.call('hugs_amg_candidates', n, m.height, m.width, x0, y0, x1, y1, h_in, w_in, lowres.to(torch.float32).contiguous(),
+              iou.to(torch.float32).contiguous(), points.to(m.device, torch.float32).contiguous(), c.pred_iou_thresh, c.stability_score_thresh,
+              c.stability_score_offset, mask_threshold, m.len, b['iou'].shape[0], b['masks_bits'], b['boxes'], b['iou'], b['stability'],
+              b['area'], b['points'], b['crop_boxes'], kept, _amg_ws(0, y1 - y0, x1 - x0, n, m.device))
+    m.len += int(kept)
+    return int(kept)
+
+  def process_crop(self, mask_set, image, crop_box, grid):
+    """_process_crop: image [H,W,3] uint8 numpy, grid [P,2] in [0,1] (amg_point_grids).  Appends the crop's masks after its NMS."""
+    x0, y0, x1, y1 = crop_box
+    crop = image[y0:y1, x0:x1]
+    ch, cw = crop.shape[:2]
+    scale = 1024. / max(ch, cw)
+    resized = self.resize(crop, (int(ch * scale + 0.5), int(cw * scale + 0.5)))
+    self.decoder.set_image_from(self.encoder, torch.as_tensor(resized).to(self.decoder.device), (ch, cw))
+    points = torch.as_tensor(grid * [[cw, ch]]).to(self.decoder.device, torch.float32)
+    start, step = mask_set.len, int(self.config.points_per_batch)
+    for i in range(0, len(points), step):
+      lowres, iou = self.decoder.predict(points[i:i + step, None, :])
+      self.add_candidates(mask_set, lowres, iou, points[i:i + step], crop_box)
+    mask_set.nms(mask_set.iou[start:], self.config.box_nms_thresh, start)
+    return mask_set
+
+  def generate(self, image):
+    """image: the original [H,W,3] uint8 image (numpy or tensor).  Returns the MaskSet of SamAutomaticMaskGenerator.generate, in
+    its order; .label_map() of it is the (seg, num_segments) of generate_static_mask."""
+    import numpy as np
+    image = np.ascontiguousarray(image.cpu().numpy() if isinstance(image, torch.Tensor) else image)
+    if image.ndim != 3 or image.shape[-1] != 3 or image.dtype != np.uint8:
+      raise ValueError(f'image must be [H,W,3] uint8, got {image.shape} {image.dtype}')
+    c = self.config
+    boxes, layers = amg_crop_boxes(image.shape[:2], c.crop_n_layers, c.crop_overlap_ratio)
+    grids = amg_point_grids(c.points_per_side, c.crop_n_layers, c.crop_n_points_downscale_factor)
+    masks = MaskSet(*image.shape[:2], device=self.decoder.device)
+    for box, layer in zip(boxes, layers):
+      self.process_crop(masks, image, box, grids[layer])
+    if len(boxes) > 1 and masks.len:
+      cb = masks.crop_boxes
+      masks.nms(1. / ((cb[:, 2] - cb[:, 0]) * (cb[:, 3] - cb[:, 1])).to(torch.float32), c.crop_nms_thresh)
+    if c.min_mask_region_area > 0:
+      masks.remove_small_regions(c.min_mask_region_area, max(c.box_nms_thresh, c.crop_nms_thresh))
+    return masks
 
 
 def write_static_mask(path, mask):
