@@ -629,6 +629,34 @@ int hugs_amg_small_regions(int K, int H, int W, int min_area, const void* masks,
                            void* ws, void* stream);
 int hugs_amg_paint(int S, int H, int W, const void* masks, const int* boxes, const int* order, int* seg, void* stream);
 
+/* The SfM point prompts (csrc/hugs_sfmpoints.hip): generate_static_mask.py:293-336, from one image's COLMAP observations to the
+ * points hugs_sam_predict takes.  Points are [n,2] fp32 (x, y), 8-byte aligned; a distance is sqrt(dx*dx + dy*dy) with every
+ * operation rounded to fp32 on its own.  The all-pairs stages take 1 <= n <= 65536 points (-2 above) in O(n) memory.  Only
+ * hugs_sfp_same_rounds' caller reads anything back (a counter); no entry synchronises with the host.  Deterministic.
+ * hugs_sfp_ws_bytes: what 0: hugs_sfp_filter for n observations (<= 2^20); 1: the hugs_sfp_same_* pair; 2: hugs_sfp_outliers.
+ * hugs_sfp_filter: :296-309.  xys [m,2] float64, track_len [m] int32 (len(ptsdata[id].image_ids), or -1 where point3D_id == -1).
+ *   Observation i is kept iff threshold == 0 or track_len[i] >= threshold (and >= 0); out gets clip(x * (W / cam_w), 0, W),
+ *   clip(y * (H / cam_h), 0, H) computed in float64 and rounded once to fp32, in input order; *count = how many.
+ * hugs_sfp_same_rounds + hugs_sfp_same_finish: :81-94 delete_same_points, the greedy choice in index order (point i is kept iff no
+ *   kept j < i has distance < threshold).  ws starts with 64 int32 counters: [r] = the points undecided before round r.  _rounds
+ *   runs the rounds first_round .. first_round + rounds - 1 (first_round 0 also resets ws); a round decides every point whose
+ *   closer predecessors are all decided, and is a no-op once counter [r] is 0.  _finish(last_round = rounds run so far) decides
+ *   what is left in index order, then writes the kept points in input order, their former indices and *count.
+ * hugs_sfp_outliers: :97-107 delete_outlier_points for n >= 2.  Point i is kept iff its distance to the nearest other point is
+ *   < mean + std_coefficient * std of all n (n - 1) off-diagonal distances (unbiased std), the moments summed in float64 from the
+ *   fp32 distances in a fixed order and the comparison made in float64.  ws begins with the doubles {mean, std, threshold, 0}.
+ * hugs_sfp_nearest: :331-333 with input_points = feature_points.  index [n,k] = for each point the k <= min(32, n) points at the
+ *   smallest distance (itself included, distance 0), ascending, equal distances lower index first; out [n,k,2] = their
+ *   coordinates. */
+long long hugs_sfp_ws_bytes(int what, int n);
+int hugs_sfp_filter(int m, const void* xys, const int* track_len, int threshold, int cam_h, int cam_w, int H, int W, float* out,
+                    int* count, void* ws, void* stream);
+int hugs_sfp_same_rounds(int n, const float* points, float threshold, int first_round, int rounds, void* ws, void* stream);
+int hugs_sfp_same_finish(int n, const float* points, float threshold, int last_round, float* out, int* index, int* count, void* ws,
+                         void* stream);
+int hugs_sfp_outliers(int n, const float* points, float std_coefficient, float* out, int* index, int* count, void* ws, void* stream);
+int hugs_sfp_nearest(int n, int k, const float* points, float* out, int* index, void* stream);
+
 /* test/bench forms of hugs_gemm_nt / hugs_gemm_tn with an explicit kernel selection (a call argument: no process
  * state): tile_mode 0 = the default choice (what the plain entry points use), 1 = force the 128x128-tile kernels,
  * 3 = the 256x128 NT kernel where a 256x256 one would be chosen, 5 = 256x256 without the persistent form */

@@ -92,6 +92,12 @@ _PROTOS = {
     'hugs_amg_gather': 'iqpppppps',
     'hugs_amg_small_regions': 'iiiippppips',
     'hugs_amg_paint': 'iiipppps',
+    'hugs_sfp_ws_bytes': 'ii',
+    'hugs_sfp_filter': 'ippiiiiippps',
+    'hugs_sfp_same_rounds': 'ipfiips',
+    'hugs_sfp_same_finish': 'ipfipppps',
+    'hugs_sfp_outliers': 'ipfpppps',
+    'hugs_sfp_nearest': 'iippps',
     'hugs_sm_label': 'iiipps',
     'hugs_sm_label_hist': 'iiippps',
     'hugs_sm_select_erode': 'iippiiiips',
@@ -207,6 +213,7 @@ class _Lib:
     self.cdll.hugs_sam_ws_bytes.restype = ctypes.c_longlong
     self.cdll.hugs_sam_enc_ws_bytes.restype = ctypes.c_longlong
     self.cdll.hugs_amg_ws_bytes.restype = ctypes.c_longlong
+    self.cdll.hugs_sfp_ws_bytes.restype = ctypes.c_longlong
 
   def declare(self, name, sig):
     _PROTOS[name] = sig

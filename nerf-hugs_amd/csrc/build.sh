@@ -16,6 +16,7 @@ for f in hugs_*.hip; do
   [ "$f" = "hugs_lpips.hip" ] && extra="-Xclang -target-feature -Xclang -packed-fp32-ops"        # (fp32 MFMA file: scalar fp32 VALU forms only)
   [ "$f" = "hugs_samencode.hip" ] && extra="-Xclang -target-feature -Xclang -packed-fp32-ops"    # (fp32 MFMA file: scalar fp32 VALU forms only)
   [ "$f" = "hugs_staticmask.hip" ] && extra="-Xclang -target-feature -Xclang -packed-fp32-ops"   # (integer / ballot file: scalar fp32 VALU forms only)
+  [ "$f" = "hugs_sfmpoints.hip" ] && extra="-ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt"      # (decisions on individually rounded fp32 distances)
   dep="$f"
   [ "$f" = "hugs_gemm_f16.hip" ] && dep="hugs_gemm.hip"      # (it is hugs_gemm.hip compiled with half operands)
   o="_obj/${f%.hip}.o"

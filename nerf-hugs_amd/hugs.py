@@ -15,8 +15,11 @@ SamImageEncoder computes that embedding from the resized image (:338, csrc/hugs_
 SamMaskGenerator computes `seg` itself: segment_anything's SamAutomaticMaskGenerator around those two (:193-201, :237-242;
 csrc/hugs_samamg.hip), with its masks bit-packed on the device in a MaskSet.
 
-Not here: box and mask prompts, RLE output, the COLMAP point filtering / K-means that choose the prompts (:293-343), the
-visualisation panels.  The PIL resize of the generator's crops is host image I/O (a replaceable callable).
+select_sfm_prompts / sfm_prompts_from_colmap choose the points add_points takes (:293-336, csrc/hugs_sfmpoints.hip): COLMAP's
+observations of the image filtered by track length, delete_same_points, delete_outlier_points, nearest_points.
+
+Not here: box and mask prompts, RLE output, the K-means reduction of the prompts (:319-326: sfm_cluster_num stays disabled, see
+select_sfm_prompts), the visualisation panels.  The PIL resize of the generator's crops is host image I/O (a replaceable callable).
 intersect_threshold is a rational (numerator, denominator): the kernels compare inter * den >= num * area in integers."""
 import dataclasses
 import fractions
@@ -39,6 +42,10 @@ class SegmentConfig:
   erode_kernel_size: int = 5
   sfm_seg_batch_size: int = 128
   sfm_use_highest_iou: bool = True
+  sfm_point_count_threshold: int = 5
+  sfm_delete_outlier_points: bool = False
+  sfm_cluster_num: int = -1
+  sfm_points_per_mask: int = 1
 
 
 def check_image_size(height, width):
@@ -174,6 +181,161 @@ class SfmAccumulator:
     out = torch.empty(self.count.shape, dtype=torch.float32, device=self.count.device)
     _lib.call('hugs_sm_box', *self.count.shape, 1, self.count, None, None, 5, 1, 0, None, out)
     return out
+
+
+MAX_SFM_POINTS = 65536       # the all-pairs stages (csrc/hugs_sfmpoints.hip)
+MAX_NEAREST = 32
+_SAME_ROUNDS_PER_READ, _SAME_MAX_ROUNDS = 4, 16
+
+
+def _sfp_ws(what, n, device):
+  size = _lib.call('hugs_sfp_ws_bytes', what, n)
+  if size < 0:
+    raise ValueError(_lib.lib().cdll.hugs_last_error().decode())
+  return torch.empty(size // 4 + 1, dtype=torch.int32, device=device)
+
+
+def _points(points):
+  if points.dim() != 2 or points.shape[-1] != 2:
+    raise ValueError(f'points must be [n,2], got {tuple(points.shape)}')
+  return points.to(torch.float32).contiguous()
+
+
+def _kept(n, device):
+  return (torch.empty((n, 2), dtype=torch.float32, device=device), torch.empty(n, dtype=torch.int32, device=device),
+          torch.zeros(1, dtype=torch.int32, device=device))
+
+
+def sfm_feature_points(xys, track_len, camera_size, image_size, point_count_threshold=5, device='cuda'):
+  """:296-309.  xys [m,2] float64 (COLMAP keypoints in camera pixels), track_len [m] int32 (the length of the keypoint's 3-D point
+  track, -1 without a 3-D point), camera_size and image_size (height, width).  Keeps observation i iff the threshold is 0 or
+  track_len[i] >= threshold, and returns [n,2] float32 on the device in input order: clip(x * (W / cam_w), 0, W), clip(y * (H /
+  cam_h), 0, H) in float64, rounded once -- bit for bit what the reference's numpy + torch.tensor(..., float32) gives."""
+  xys = torch.as_tensor(xys, dtype=torch.float64).to(device).contiguous()
+  track_len = torch.as_tensor(track_len).to(device, torch.int32).contiguous()
+  m = track_len.shape[0]
+  if xys.dim() != 2 or tuple(xys.shape) != (m, 2):
+    raise ValueError(f'xys must be [m,2] and track_len [m], got {tuple(xys.shape)} and {tuple(track_len.shape)}')
+  (cam_h, cam_w), (h, w) = (int(v) for v in camera_size), (int(v) for v in image_size)
+  if m == 0:
+    return torch.empty((0, 2), dtype=torch.float32, device=xys.device)
+  ws = _sfp_ws(0, m, xys.device)
+  out, _, count = _kept(m, xys.device)
+  # (the binding keeps float64 tensors away from the fp32 kernels; this entry reads doubles, so it gets the same bytes as int64)
+  _lib.call('hugs_sfp_filter', m, xys.view(torch.int64), track_len, int(point_count_threshold), cam_h, cam_w, h, w, out, count, ws)
+  return out[:int(count)]
+
+
+def delete_same_points(points, distance_threshold=0.1, stats=None):
+  """:81-94, the reference's greedy loop exactly: point 0 is kept and point i is kept iff no kept j < i is closer than the
+  threshold (fp32 distances, the threshold rounded to fp32; dropped points suppress nobody).  Returns (the kept points in input
+  order, their former indices int32).  The device decides in rounds -- every undecided point whose closer predecessors are all
+  decided -- and the host reads the undecided count every few rounds; a dependency chain deeper than 16 rounds is finished by a
+  walk in index order.  stats: a dict that receives 'rounds' (rounds run until nothing was undecided) and 'walked' (points left
+  to the walk)."""
+  points = _points(points)
+  n = points.shape[0]
+  if n == 0:
+    return points, torch.empty(0, dtype=torch.int32, device=points.device)
+  ws = _sfp_ws(1, n, points.device)
+  rounds, left = 0, n
+  while left and rounds < _SAME_MAX_ROUNDS:
+    _lib.call('hugs_sfp_same_rounds', n, points, distance_threshold, rounds, _SAME_ROUNDS_PER_READ, ws)
+    rounds += _SAME_ROUNDS_PER_READ
+    left = int(ws[rounds])
+  out, index, count = _kept(n, points.device)
+  _lib.call('hugs_sfp_same_finish', n, points, distance_threshold, rounds, out, index, count, ws)
+  if stats is not None:
+    undecided = ws[:rounds + 1].tolist()
+    stats['rounds'] = undecided.index(0) if 0 in undecided else rounds
+    stats['walked'] = left
+  count = int(count)
+  return out[:count], index[:count]
+
+
+def delete_outlier_points(points, std_coefficient=3.0):
+  """:97-107: keeps the points whose distance to the nearest other point is < mean + std_coefficient * std over all n (n - 1)
+  pairwise distances (fp32 distances; the moments and the comparison in float64, summed in a fixed order).  Returns (the kept
+  points in input order, their former indices int32).  Two points are both dropped, as in the reference (std = 0, d < d is
+  false); with fewer than two the reference fails on an empty min, here the input comes back unchanged."""
+  points = _points(points)
+  n = points.shape[0]
+  if n < 2:
+    return points, torch.arange(n, dtype=torch.int32, device=points.device)
+  out, index, count = _kept(n, points.device)
+  _lib.call('hugs_sfp_outliers', n, points, std_coefficient, out, index, count, _sfp_ws(2, n, points.device))
+  count = int(count)
+  return out[:count], index[:count]
+
+
+def nearest_points(points, k, return_index=False):
+  """:331-333 with input_points = feature_points: [n, min(k, n), 2], each point followed by its nearest others in ascending
+  distance (with return_index also their indices [n, min(k, n)] int32).  Equal distances go lower index first -- the reference's
+  argsort is unstable there, so its order among exact ties (and whether a duplicate precedes the point itself) is unspecified.
+  k <= 32."""
+  points = _points(points)
+  n, k = points.shape[0], int(k)
+  if not 1 <= k <= MAX_NEAREST:
+    raise ValueError(f'nearest_points: k = {k} outside 1..{MAX_NEAREST}')
+  k = min(k, n)
+  out = torch.empty((n, k, 2), dtype=torch.float32, device=points.device)
+  index = torch.empty((n, k), dtype=torch.int32, device=points.device)
+  if n:
+    _lib.call('hugs_sfp_nearest', n, k, points, out, index)
+  return (out, index) if return_index else out
+
+
+def select_sfm_prompts(xys, track_len, camera_size, image_size, config=None, device='cuda'):
+  """:293-336 for one image: sfm_feature_points (config.sfm_point_count_threshold), delete_same_points, delete_outlier_points when
+  config.sfm_delete_outlier_points, then nearest_points for config.sfm_points_per_mask > 1.  Returns the prompts [N,P,2] float32
+  on the device for SfmAccumulator.add_points ([0,1,2] when no point survives the filter).
+  sfm_cluster_num: <= 0 or >= the number of points is "disabled" (:319).  0 < sfm_cluster_num < n raises ValueError: at :325 the
+  reference assigns the unique cluster INDICES (an argsort over the cluster axis) to input_points, not points, so that path
+  cannot produce [n,1,2] prompts, and no shipped config enables it; K-means is not built."""
+  config = config if config is not None else SegmentConfig()
+  points = sfm_feature_points(xys, track_len, camera_size, image_size, config.sfm_point_count_threshold, device)
+  if points.shape[0] == 0:
+    return points.reshape(0, 1, 2)
+  points, _ = delete_same_points(points)
+  if config.sfm_delete_outlier_points:
+    points, _ = delete_outlier_points(points)
+  if 0 < config.sfm_cluster_num < points.shape[0]:
+    raise ValueError(f'sfm_cluster_num = {config.sfm_cluster_num} with {points.shape[0]} points: the reference\'s K-means path '
+                     '(generate_static_mask.py:319-326) yields cluster indices instead of points and is not supported; leave it <= 0')
+  if config.sfm_points_per_mask > 1 and points.shape[0]:
+    return nearest_points(points, config.sfm_points_per_mask)
+  return points.unsqueeze(1)
+
+
+def read_sfm_model(colmap_dir):
+  """The parts of a COLMAP sparse model the prompts need, read once for all images: (cameras, images with their 2-D observations,
+  track length per 3-D point)."""
+  import os
+  from .internal import colmap
+  return (colmap.read_cameras_binary(os.path.join(colmap_dir, 'cameras.bin')),
+          colmap.read_images_points2D(os.path.join(colmap_dir, 'images.bin')),
+          colmap.read_points3D_track_lengths(os.path.join(colmap_dir, 'points3D.bin')))
+
+
+def sfm_observations(model, image_name):
+  """Host side of :294-303.  model: a COLMAP directory or read_sfm_model's tuple; image_name: the image file's stem (:212).
+  Returns numpy (xys float64 [m,2], track_len int32 [m] with -1 where the keypoint has no 3-D point, (cam_h, cam_w))."""
+  import os
+  import numpy as np
+  cameras, images, tracks = read_sfm_model(model) if isinstance(model, (str, os.PathLike)) else model
+  by_stem = {os.path.splitext(os.path.basename(name))[0]: iid for iid, (name, _, _, _) in images.items()}
+  if image_name not in by_stem:
+    raise ValueError(f'no image with the stem {image_name!r} in the COLMAP model')
+  _, camera_id, xys, ids = images[by_stem[image_name]]
+  track_len = np.array([tracks[int(p)] if p != -1 else -1 for p in ids], dtype=np.int32).reshape(-1)
+  cam = cameras[camera_id]
+  return xys, track_len, (int(cam['height']), int(cam['width']))
+
+
+def sfm_prompts_from_colmap(model, image_name, image_size, config=None, device='cuda'):
+  """COLMAP files to prompts: sfm_observations + select_sfm_prompts.  image_size = (H, W) of pred / gt."""
+  xys, track_len, camera_size = sfm_observations(model, image_name)
+  return select_sfm_prompts(xys, track_len, camera_size, image_size, config, device)
 
 
 def _sam_keys():

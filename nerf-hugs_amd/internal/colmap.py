@@ -71,6 +71,43 @@ def read_points3D_binary(path):
   return np.array(pts, np.float64).reshape(-1, 3)
 
 
+def read_images_points2D(path):
+  """images.bin with the 2-D observations read_images_binary skips: {image_id: (name, camera_id, xys float64 [m,2],
+  point3D_ids int64 [m])}, point3D_id -1 where the keypoint has no 3-D point (HuGS/generate_static_mask.py:296-298)."""
+  obs = np.dtype([('xy', '<f8', 2), ('id', '<i8')])
+  imgs = {}
+  with open(path, 'rb') as f:
+    (n,) = _rd(f, 'Q')
+    for _ in range(n):
+      (iid,) = _rd(f, 'i')
+      f.seek(7 * 8, os.SEEK_CUR)
+      (cid,) = _rd(f, 'i')
+      name = b''
+      while True:
+        c = f.read(1)
+        if c in (b'\x00', b''):
+          break
+        name += c
+      (m,) = _rd(f, 'Q')
+      rows = np.frombuffer(f.read(obs.itemsize * m), obs, m)
+      imgs[iid] = (name.decode(), cid, rows['xy'].astype(np.float64).reshape(-1, 2), rows['id'].astype(np.int64))
+  return imgs
+
+
+def read_points3D_track_lengths(path):
+  """points3D.bin: {point3D_id: track length}, the len(ptsdata[id].image_ids) of generate_static_mask.py:303."""
+  lens = {}
+  with open(path, 'rb') as f:
+    (n,) = _rd(f, 'Q')
+    for _ in range(n):
+      (pid,) = _rd(f, 'Q')
+      f.seek(24 + 3 + 8, os.SEEK_CUR)
+      (tl,) = _rd(f, 'Q')
+      f.seek(8 * tl, os.SEEK_CUR)
+      lens[pid] = tl
+  return lens
+
+
 def qvec_to_rotmat(q):
   w, x, y, z = q
   return np.array([[1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * w * z, 2 * z * x + 2 * w * y],
